@@ -16,8 +16,14 @@ rank transforms its own independent batches (weak scaling, no data-path collecti
 limbs are independent).  The C5 leg scatters one fixed batch of bootstraps over the
 ranks and gathers the results (strong scaling of that batch, RCCL over xGMI).
 
+A plain run (`--gpus 1 --steps N --warmup W`) does only that: set up, warm up, time the N steps,
+print the result line.  `--dump-outputs DIR` also writes the batch of the last timed step.  With
+`--full` the run goes on to everything below and adds it to the result line:
+
+single_stream: the same steps on one stream.
 roofline: the forward transform (column pass + row pass kernels) timed with HIP events on
 the stream the kernels run on; achieved = 46,137,344 B / average forward duration.
+c3, c4, c5: the HE multiply chain, the bootstrap latency and the sharded bootstrap batch.
 cpu_baseline: the oracle's scalar C restatement (oracle/liboracle.so) on a bounded sample.
 """
 import argparse
@@ -473,11 +479,54 @@ def _kernel_sum_ms():
 KERNEL_SUM_MS = _kernel_sum_ms()
 
 
+def headline(args, world, value, elapsed, nbuf, K):
+    """The result line of the timed C2 steps (every run prints these fields; --full adds to them)."""
+    return {
+        "metric": "NTT GB/s vs HBM roofline (fwd+inv NTT, N=2^16, L=44)",
+        "value": round(value, 2),
+        "unit": "GB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic uniform residues in [0, q_i), seed 0x5EED",
+        "config": {
+            "workload": "C2: forward+inverse negacyclic NTT, N=65536, 44 RNS limbs of the 3_ckks.cu C3 chain",
+            "poly_modulus_degree": N,
+            "limbs": L,
+            "batch_per_rank": 1,
+            "buffer_ring": nbuf,
+            "streams_per_rank": K,
+            "parallelism": f"replicas x{world} (independent batches per rank, dealt to {K} HIP streams)",
+        },
+    }
+
+
+def dump_outputs(path, batch):
+    """--dump-outputs: the [44][65536] batch the last timed step transformed in place (forward, then
+    inverse NTT: what the caller of that step holds afterwards), rank 0's.  Its uint64 residues
+    (< 2^60) do not fit a float64, so each coefficient is written as two exact float64 values, its
+    low and its high 32 bits: 2 x 23 MB."""
+    a = batch.cpu().numpy().view(np.uint64).reshape(L, N)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "c2_last_step_lo32.npy"), (a & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "c2_last_step_hi32.npy"), (a >> np.uint64(32)).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline C2 steps also run the single-stream and roofline timings, the C3, C4 and C5 "
+                         "legs and the CPU baseline (the --no-* and --c5-* options select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--c2-streams", type=int, default=3, help="C2: HIP streams the independent batches are dealt to")
     ap.add_argument("--no-c3", action="store_true", help="skip the C3 (mult+relin+rescale) leg")
@@ -560,6 +609,21 @@ def main():
         return time.perf_counter() - t0
 
     elapsed = timed(K)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, ring[(args.warmup + args.steps - 1) % nbuf])
+    if not args.full:
+        # a plain run ends here: the headline figure of the timed steps and nothing else
+        for ls in lanes:
+            stream.wait_stream(ls)
+        elapsed, = max_over_ranks(dist if world > 1 else None, [elapsed], "cuda")
+        value = job_throughput(2 * BYTES_PER_TRANSFORM * args.steps, world, elapsed) / 1e9
+        if rank == 0:
+            print(json.dumps(headline(args, world, value, elapsed, nbuf, K)), flush=True)
+        tables.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     elapsed_1 = timed(1) if K > 1 else elapsed  # the same steps on one stream, for reference
     for ls in lanes:
         stream.wait_stream(ls)
@@ -597,27 +661,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "NTT GB/s vs HBM roofline (fwd+inv NTT, N=2^16, L=44)",
-            "value": round(value, 2),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic uniform residues in [0, q_i), seed 0x5EED",
-            "config": {
-                "workload": "C2: forward+inverse negacyclic NTT, N=65536, 44 RNS limbs of the 3_ckks.cu C3 chain",
-                "poly_modulus_degree": N,
-                "limbs": L,
-                "batch_per_rank": 1,
-                "buffer_ring": nbuf,
-                "streams_per_rank": K,
-                "parallelism": f"replicas x{world} (independent batches per rank, dealt to {K} HIP streams)",
-            },
+            **headline(args, world, value, elapsed, nbuf, K),
             # the same steps on one stream (no overlap of independent batches): the per-transform rate
             "single_stream": {"value": round(value_1, 2), "ms_per_step": round(elapsed_1 / args.steps * 1e3, 5),
                               "per_transform_ms": round(elapsed_1 / args.steps * 1e3 / 2, 5)},

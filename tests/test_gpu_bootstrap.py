@@ -239,7 +239,7 @@ def test_bench_c5_leg_single_gpu():
     bootstrap on lanes, gather, decrypt-check every result."""
     import json
     import sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-c3",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-c3",
                           "--no-c4", "--no-cpu-baseline", "--c5-batch", "8", "--c5-lanes", "4",
                           "--c5-key-seed", bytes(range(32)).hex()],
                          capture_output=True, text=True, timeout=115)

@@ -5,7 +5,7 @@
 # Steps run in order; the chain stops at the first failure (every GPU step has its own time
 # limit).  Output lands under gpurun_out/$TAG/.  Steps:
 #   tests        pytest -m gpu (TESTS=... selects files/-k, default the whole suite)
-#   bench        python bench.py $BENCH_ARGS          -> bench.json / bench.log
+#   bench        python bench.py $BENCH_ARGS          -> bench.json / bench.log (--full in BENCH_ARGS for every leg)
 #   stats        rocprofv3 --kernel-trace --stats of $PROF_CMD (default: bench.py C2 only)
 #   boot         the bootstrap example ($RUNS runs) -> boot.txt
 #   bootstats    rocprofv3 kernel stats of the bootstrap example (warm runs)
@@ -18,7 +18,7 @@ TAG=${TAG:-run}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 PY=python3
-DEFAULT_PROF="$PY $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-c3 --no-c4 --no-c5"
+DEFAULT_PROF="$PY $PWD/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-c3 --no-c4 --no-c5"
 
 step_tests() {
   timeout -k 10 ${T_TESTS:-900} $PY -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 300 --timeout-method thread \
