@@ -332,6 +332,45 @@ int phantom_poly_op(const phantom_context *ctx, int op, const uint64_t *a, const
 int phantom_switch_modulus_raise(const phantom_context *ctx, const uint64_t *in_q0, uint64_t *out,
                                  size_t coeff_modulus_size, hipStream_t stream);
 
+/* ---- CKKS encode / decode on the device (PhantomCKKSEncoder, src/ckks.cu:45-521) --------------
+ * Slot j sits at the root zeta^(5^j) of X^N + 1 and its conjugate at zeta^(-5^j).  Complex data is
+ * interleaved (re, im) doubles; plaintexts are [limbs][n] words, `count` of them back to back.
+ * Everything is enqueued on `stream`; scratch comes from the engine's pool on that stream.  Bad
+ * arguments (scale <= 0, too many values, a sparse slot count that is no power of two <= N/2, a
+ * chain index past the end, ext at chain 0) return PHANTOM_ERR_INVALID_ARGUMENT before any launch.
+ * dev_overflow (device int, may be NULL) is set non-zero, never cleared, when some value times the
+ * scale is not finite or reaches 2^1000 (the host encoder's "encoded values are too large"); the
+ * residues written are then unspecified. */
+/* The canonical embedding alone, in FP64: the special FFT pair of src/fft.cu:651-815
+ * (special_fft_backward / special_fft_forward, called at src/ckks.cu:143, 509) as one size-N transform.  ns = sparse_slots, or N/2 when 0.
+ * forward == 0: in [count][ns] complex -> out [count][N] real coefficients, 1/N included, not
+ * scaled; the ns values fill every block of ns slots (set_sparse_encode, include/ckks.h:82-117).
+ * forward != 0: in [count][N] reals -> out [count][ns] complex, the first ns slots. */
+int phantom_ckks_embed(const phantom_context *ctx, int forward, const double *in, double *out, size_t sparse_slots,
+                       size_t count, hipStream_t stream);
+/* decompose_array (src/rns_base.cu:49-170; called at src/ckks.cu:171, 348):
+ * out[p][i][k] = round_half_even(coeffs[p][k] * scale) mod q_i (negative values as q_i - v), exact
+ * for every product below 2^1000, over the Ql basis of chain_index, followed by the special primes
+ * when ext != 0 (encode_internal_ext, src/ckks.cu:276-353); ntt_form != 0 applies the forward NTT
+ * (src/ckks.cu:174, 350). */
+int phantom_ckks_round_rns(const phantom_context *ctx, size_t chain_index, int ext, const double *coeffs, double scale,
+                           size_t count, int ntt_form, uint64_t *out, int *dev_overflow, hipStream_t stream);
+/* compose_array (src/rns_base.cu:173-260) after the inverse NTT (src/ckks.cu:494-499): plain_ntt
+ * [count][Ql][N] (NTT form, not modified) -> coeffs [count][N], the centred integer in (-Q/2, Q/2]
+ * of each coefficient as a double (exact below 2^53, else within one ulp of correct rounding), not
+ * divided by the scale.  chain_index >= 1. */
+int phantom_ckks_compose(const phantom_context *ctx, size_t chain_index, const uint64_t *plain_ntt, size_t count,
+                         double *coeffs, hipStream_t stream);
+/* PhantomCKKSEncoder::encode_internal (src/ckks.cu:103-178): values [count][num_values] complex
+ * (num_values <= ns, zero-padded) -> out [count][limbs][N], NTT form */
+int phantom_ckks_encode(const phantom_context *ctx, size_t chain_index, int ext, const double *values,
+                        size_t num_values, size_t sparse_slots, double scale, size_t count, uint64_t *out,
+                        int *dev_overflow, hipStream_t stream);
+/* PhantomCKKSEncoder::decode_internal (src/ckks.cu:456-521): plain [count][Ql][N] (NTT form, not
+ * modified) -> values [count][N/2] complex = embedding(centred coefficients / scale) */
+int phantom_ckks_decode(const phantom_context *ctx, size_t chain_index, const uint64_t *plain, double scale,
+                        size_t count, double *values, hipStream_t stream);
+
 /* ---- bootstrapping sessions (bootstrapping/bootstrapping_example.cu:69-160; src/bootstrap.cu) ----
  * A session is the SimpleBootstrapExample set-up as one object: N = 2^log_n, Q = {60, depth x 59},
  * P = special x 60 (CoeffModulus::Create), scale 2^59, levelBudget {enc, dec}, num_slots slots

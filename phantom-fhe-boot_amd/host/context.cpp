@@ -1,6 +1,7 @@
 #include "context.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <stdexcept>
 #include <thread>
@@ -143,6 +144,84 @@ const uint64_t* PhantomContext::monomial_ntt(uint32_t power, size_t L) const {
   PHX_CHECK(phx::ntt_forward(ntt_->get(), d.get(), d.get(), phx::LimbMap::contiguous(static_cast<int>(L), 0), stream_.s));
   PHX_CHECK(hipStreamSynchronize(stream_.s));
   return monomials_.emplace(key, std::move(d)).first->second.get();
+}
+
+phx::EmbedTables PhantomContext::embed_tables() const {
+  std::lock_guard<std::mutex> lk(cache_mu_);
+  if (!embed_zeta_) {
+    const size_t m = 2 * n_;
+    std::vector<double2> zeta(m);
+    for (size_t j = 0; j < m; ++j) {
+      const double a = 2.0 * M_PI * static_cast<double>(j) / static_cast<double>(m);
+      zeta[j] = make_double2(std::cos(a), std::sin(a));
+    }
+    // position (5^j mod 2n - 1) / 2 holds slot j, its mirror n - 1 - that the conjugate
+    std::vector<uint32_t> slot_of(n_);
+    uint64_t p = 1;
+    for (size_t j = 0; j < n_ / 2; ++j) {
+      const size_t idx = static_cast<size_t>((p - 1) / 2);
+      slot_of[idx] = static_cast<uint32_t>(j);
+      slot_of[n_ - 1 - idx] = static_cast<uint32_t>(j) | phx::EmbedTables::kConjBit;
+      p = (p * 5) % m;
+    }
+    DeviceBuffer<uint32_t> d;
+    d.upload(slot_of, stream_.s);
+    embed_slot_of_ = std::move(d);
+    DeviceBuffer<double2> z;
+    z.upload(zeta, stream_.s);
+    embed_zeta_ = std::move(z);
+  }
+  phx::EmbedTables t;
+  t.n = n_;
+  t.log_n = arith::log2_exact(n_);
+  t.zeta = embed_zeta_.get();
+  t.slot_of = embed_slot_of_.get();
+  return t;
+}
+
+phx::ComposeTables PhantomContext::compose_tables(size_t chain_index) const {
+  if (chain_index < 1 || chain_index >= data_.size()) throw std::invalid_argument("invalid chain index");
+  const std::vector<uint64_t>& q = data_[chain_index]->moduli();
+  const size_t L = q.size();
+  if (L > static_cast<size_t>(phx::kMaxComposeLimbs)) throw std::invalid_argument("too many limbs to compose");
+  std::lock_guard<std::mutex> lk(cache_mu_);
+  auto it = compose_.find(chain_index);
+  if (it == compose_.end()) {
+    using namespace arith;
+    // layout: prefix [L][L], prefix_shoup [L][L], inv_prefix [L] + Shoup [L], half_digits [L]
+    std::vector<uint64_t> h(2 * L * L + 3 * L, 0);
+    uint64_t* prefix = h.data();
+    uint64_t* prefix_shoup = prefix + L * L;
+    uint64_t* inv_prefix = prefix_shoup + L * L;
+    uint64_t* half = inv_prefix + 2 * L;
+    for (size_t i = 0; i < L; ++i) {
+      uint64_t pr = 1 % q[i];
+      for (size_t j = 0; j < i; ++j) {
+        prefix[i * L + j] = pr;
+        prefix_shoup[i * L + j] = shoup(pr, q[i]);
+        pr = mul_mod(pr, q[j] % q[i], q[i]);
+      }
+      inv_prefix[i] = i ? inv_mod(pr, q[i]) : 1;
+      inv_prefix[L + i] = shoup(inv_prefix[i], q[i]);
+    }
+    // mixed-radix digits of (Q - 1) / 2, whose residue mod q_i is (q_i - 1) / 2
+    for (size_t i = 0; i < L; ++i) {
+      uint64_t acc = 0;
+      for (size_t j = 0; j < i; ++j) acc = (acc + mul_mod(half[j] % q[i], prefix[i * L + j], q[i])) % q[i];
+      const uint64_t d = ((q[i] - 1) / 2 + q[i] - acc) % q[i];
+      half[i] = mul_mod(d, inv_prefix[i], q[i]);
+    }
+    DeviceBuffer<uint64_t> d;
+    d.upload(h, stream_.s);
+    it = compose_.emplace(chain_index, std::move(d)).first;
+  }
+  phx::ComposeTables c;
+  c.L = static_cast<int>(L);
+  c.prefix = it->second.get();
+  c.prefix_shoup = c.prefix + L * L;
+  c.inv_prefix = c.prefix_shoup + L * L;
+  c.half_digits = c.inv_prefix + 2 * L;
+  return c;
 }
 
 }  // namespace phantom

@@ -14,6 +14,7 @@
 #include "modulus.h"
 #include "ntt_tables.h"
 #include "rns_tool.h"
+#include "../csrc/encode.h"
 
 namespace phantom {
 
@@ -177,6 +178,11 @@ class PhantomContext {
   const uint32_t* galois_block_inv(uint32_t elt) const { return galois_perm(elt) + n_; }
   // NTT(X^power) over the first L key moduli ([L][n]), cached per context
   const uint64_t* monomial_ntt(uint32_t power, size_t L) const;
+  // tables of the device encoder (csrc/encode.h), built once per context on first use: the
+  // embedding's roots and slot placement, and the composition constants of `chain_index`'s Ql
+  // basis.  The first use uploads on the context's own stream and waits for it.
+  phx::EmbedTables embed_tables() const;
+  phx::ComposeTables compose_tables(size_t chain_index) const;
 
   // Opt-in mean-unbiased moddowns at every level (RnsTool::set_unbias): off by default, where each
   // division is the reference's bit for bit.  PHX_UNBIASED_MODDOWN=1 in the environment turns it
@@ -197,6 +203,9 @@ class PhantomContext {
   mutable std::mutex cache_mu_;
   mutable std::map<uint32_t, DeviceBuffer<uint32_t>> perms_;
   mutable std::map<std::pair<uint32_t, size_t>, DeviceBuffer<uint64_t>> monomials_;
+  mutable DeviceBuffer<double2> embed_zeta_;
+  mutable DeviceBuffer<uint32_t> embed_slot_of_;
+  mutable std::map<size_t, DeviceBuffer<uint64_t>> compose_;  // per chain index, see compose_tables
   DeviceBuffer<uint64_t> ones_ntt_;  // NTT(1, ..., 1) over Q, for the unbiased moddown
   bool unbiased_ = false;
 };

@@ -3,9 +3,12 @@
 #include <algorithm>
 #include <cmath>
 #include <stdexcept>
+#include <string>
 #include <thread>
 
+#include "../csrc/encode.h"
 #include "../csrc/ntt.h"
+#include "buffer.h"
 #include "hip_check.h"
 #include "numth.h"
 
@@ -284,6 +287,223 @@ void PhantomCKKSEncoder::encode_sparse(const PhantomContext& ctx, const std::vec
 void PhantomCKKSEncoder::encode_sparse(const PhantomContext& ctx, const std::vector<double>& values, double scale,
                                        PhantomPlaintext& out, size_t chain_index) const {
   encode_sparse(ctx, std::vector<std::complex<double>>(values.begin(), values.end()), scale, out, chain_index);
+}
+
+// ---- the device encoder (csrc/encode.h) ------------------------------------------------------
+
+namespace {
+// plaintexts per slice of a batch: bounds the scratch (1.5 MiB of FP64 per plaintext at N = 2^16,
+// plus the residues where the outputs are not contiguous)
+constexpr size_t kEncodeSlice = 32;
+
+inline void enc_ok(hipError_t e, const char* what) {
+  if (e == hipErrorInvalidValue) throw std::invalid_argument(std::string(what) + ": unsupported shape");
+  if (e != hipSuccess) throw hip_error(e, what);
+}
+}  // namespace
+
+phx::LimbMap encode_limb_map(const PhantomContext& ctx, size_t chain_index, bool ext) {
+  if (chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  const size_t size_Ql = ctx.get_context_data(chain_index).coeff_modulus_size();
+  if (!ext) return phx::LimbMap::contiguous(static_cast<int>(size_Ql), 0);
+  if (chain_index == 0) throw std::invalid_argument("the key level has no extended basis");
+  phx::LimbMap m;
+  m.num_limbs = static_cast<int>(size_Ql + ctx.size_P());
+  m.split = static_cast<int>(size_Ql);
+  m.first_a = 0;
+  m.first_b = static_cast<int>(ctx.size_Q());
+  return m;
+}
+
+static void check_sparse(size_t n, size_t sparse_slots, size_t num_values) {
+  const size_t ns = sparse_slots ? sparse_slots : n / 2;
+  if (ns > n / 2 || (ns & (ns - 1))) throw std::invalid_argument("sparse slot count must be a power of two <= N/2");
+  if (num_values > ns) throw std::invalid_argument("more values than slots");
+}
+
+void embed_raw(const PhantomContext& ctx, bool forward, const void* in, void* out, size_t sparse_slots, size_t count,
+               hipStream_t s) {
+  const size_t n = ctx.poly_degree();
+  check_sparse(n, sparse_slots, 0);
+  if (count == 0) return;
+  if (!in || !out) throw std::invalid_argument("null pointer");
+  const size_t ns = sparse_slots ? sparse_slots : n / 2;
+  const phx::EmbedTables t = ctx.embed_tables();
+  for (size_t p = 0; p < count; p += kEncodeSlice) {
+    const size_t c = std::min(kEncodeSlice, count - p);
+    DeviceBuffer<double2> work(c * n, s);
+    if (forward)
+      enc_ok(phx::embed_forward(t, static_cast<const double*>(in) + p * n, 1.0, sparse_slots,
+                                static_cast<double2*>(out) + p * ns, work.get(), c, s),
+             "embedding");
+    else
+      enc_ok(phx::embed_inverse(t, static_cast<const double2*>(in) + p * ns, ns, sparse_slots,
+                                static_cast<double*>(out) + p * n, work.get(), c, s),
+             "embedding");
+  }
+}
+
+void round_rns_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const double* coeffs, double scale,
+                   size_t count, bool ntt_form, uint64_t* out, int* dev_overflow, hipStream_t s) {
+  if (!(scale > 0)) throw std::invalid_argument("scale must be positive");
+  const phx::LimbMap map = encode_limb_map(ctx, chain_index, ext);
+  if (count == 0) return;
+  if (!coeffs || !out) throw std::invalid_argument("null pointer");
+  if (count > 0x7fffffffu) throw std::invalid_argument("batch too large");
+  enc_ok(phx::round_to_rns(ctx.gpu_rns_tables(), coeffs, scale, out, map, count, dev_overflow, s), "round and split");
+  if (ntt_form)
+    enc_ok(phx::ntt_forward(ctx.gpu_rns_tables(), out, out, map.batched(static_cast<int>(count)), s), "encode NTT");
+}
+
+void encode_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const std::complex<double>* values,
+                size_t num_values, size_t sparse_slots, double scale, size_t count, uint64_t* out,
+                uint64_t* const* outs, int* dev_overflow, hipStream_t s) {
+  if (!(scale > 0)) throw std::invalid_argument("scale must be positive");
+  const size_t n = ctx.poly_degree();
+  check_sparse(n, sparse_slots, num_values);
+  const phx::LimbMap map = encode_limb_map(ctx, chain_index, ext);
+  if (count == 0) return;
+  if ((!values && num_values) || (!out && !outs)) throw std::invalid_argument("null pointer");
+  const size_t words = static_cast<size_t>(map.num_limbs) * n;
+  const phx::EmbedTables t = ctx.embed_tables();
+  const phx::NttTables& ntt = ctx.gpu_rns_tables();
+  for (size_t p = 0; p < count; p += kEncodeSlice) {
+    const size_t c = std::min(kEncodeSlice, count - p);
+    DeviceBuffer<double2> work(c * n, s);
+    DeviceBuffer<double> coeffs(c * n, s);
+    enc_ok(phx::embed_inverse(t, reinterpret_cast<const double2*>(values) + p * num_values, num_values, sparse_slots,
+                              coeffs.get(), work.get(), c, s),
+           "embedding");
+    if (out) {
+      // contiguous outputs: split in place, one batched NTT
+      uint64_t* o = out + p * words;
+      enc_ok(phx::round_to_rns(ntt, coeffs.get(), scale, o, map, c, dev_overflow, s), "round and split");
+      enc_ok(phx::ntt_forward(ntt, o, o, map.batched(static_cast<int>(c)), s), "encode NTT");
+    } else {
+      // separate plaintexts: split into scratch, the NTT of each writes its plaintext
+      DeviceBuffer<uint64_t> res(c * words, s);
+      enc_ok(phx::round_to_rns(ntt, coeffs.get(), scale, res.get(), map, c, dev_overflow, s), "round and split");
+      for (size_t i = 0; i < c; ++i)
+        enc_ok(phx::ntt_forward(ntt, res.get() + i * words, outs[p + i], map, s), "encode NTT");
+    }
+  }
+}
+
+void compose_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* plain,
+                 const uint64_t* const* plains, size_t count, double mul, double* coeffs, hipStream_t s) {
+  const phx::ComposeTables ct = ctx.compose_tables(chain_index);
+  if (count == 0) return;
+  if ((!plain && !plains) || !coeffs) throw std::invalid_argument("null pointer");
+  const size_t n = ctx.poly_degree(), words = static_cast<size_t>(ct.L) * n;
+  const phx::NttTables& ntt = ctx.gpu_rns_tables();
+  const phx::LimbMap map = phx::LimbMap::contiguous(ct.L, 0);
+  for (size_t p = 0; p < count; p += kEncodeSlice) {
+    const size_t c = std::min(kEncodeSlice, count - p);
+    DeviceBuffer<uint64_t> tmp(c * words, s);  // coefficient form; the plaintext is left as it is
+    if (plain)
+      enc_ok(phx::ntt_inverse(ntt, plain + p * words, tmp.get(), map.batched(static_cast<int>(c)), nullptr, nullptr, s),
+             "decode INTT");
+    else
+      for (size_t i = 0; i < c; ++i)
+        enc_ok(phx::ntt_inverse(ntt, plains[p + i], tmp.get() + i * words, map, nullptr, nullptr, s), "decode INTT");
+    enc_ok(phx::compose_centred(ntt, ct, tmp.get(), mul, coeffs + p * n, c, s), "compose");
+  }
+}
+
+void decode_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* plain, const uint64_t* const* plains,
+                double scale, size_t count, std::complex<double>* values, hipStream_t s) {
+  if (!(scale > 0)) throw std::invalid_argument("scale must be positive");
+  (void)ctx.compose_tables(chain_index);  // validates the chain index before anything is enqueued
+  if (count == 0) return;
+  if (!values) throw std::invalid_argument("null pointer");
+  const size_t n = ctx.poly_degree();
+  const phx::EmbedTables t = ctx.embed_tables();
+  for (size_t p = 0; p < count; p += kEncodeSlice) {
+    const size_t c = std::min(kEncodeSlice, count - p);
+    DeviceBuffer<double> coeffs(c * n, s);
+    DeviceBuffer<double2> work(c * n, s);
+    const size_t words = ctx.get_context_data(chain_index).coeff_modulus_size() * n;
+    compose_raw(ctx, chain_index, plain ? plain + p * words : nullptr, plains ? plains + p : nullptr, c, 1.0 / scale,
+                coeffs.get(), s);
+    enc_ok(phx::embed_forward(t, coeffs.get(), 1.0, 0, reinterpret_cast<double2*>(values) + p * (n / 2), work.get(),
+                              c, s),
+           "embedding");
+  }
+}
+
+void PhantomCKKSEncoder::encode_device(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                       size_t num_values, double scale, PhantomPlaintext& out, size_t chain_index,
+                                       int* dev_overflow) const {
+  (void)encode_limb_map(ctx, chain_index, false);
+  hipStream_t s = ctx.stream();
+  out.resize(ctx, chain_index, s);
+  out.set_scale(scale);
+  uint64_t* o = out.data();
+  encode_raw(ctx, chain_index, false, dev_values, num_values, 0, scale, 1, o, nullptr, dev_overflow, s);
+}
+
+void PhantomCKKSEncoder::encode_sparse_device(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                              size_t num_values, double scale, PhantomPlaintext& out,
+                                              size_t chain_index, int* dev_overflow) const {
+  (void)encode_limb_map(ctx, chain_index, false);
+  check_sparse(n_, sparse_slots_, num_values);
+  hipStream_t s = ctx.stream();
+  out.resize(ctx, chain_index, s);
+  out.set_scale(scale);
+  encode_raw(ctx, chain_index, false, dev_values, num_values, sparse_slots_, scale, 1, out.data(), nullptr,
+             dev_overflow, s);
+}
+
+void PhantomCKKSEncoder::encode_ext_device(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                           size_t num_values, double scale, PhantomPlaintext& out, size_t chain_index,
+                                           int* dev_overflow) const {
+  const phx::LimbMap map = encode_limb_map(ctx, chain_index, true);
+  hipStream_t s = ctx.stream();
+  out.resize_ext(ctx, chain_index, static_cast<size_t>(map.num_limbs), s);
+  out.set_scale(scale);
+  encode_raw(ctx, chain_index, true, dev_values, num_values, 0, scale, 1, out.data(), nullptr, dev_overflow, s);
+}
+
+void PhantomCKKSEncoder::encode_ext_device(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                           double scale, std::span<PhantomPlaintext> outs, size_t chain_index,
+                                           int* dev_overflow) const {
+  const phx::LimbMap map = encode_limb_map(ctx, chain_index, true);
+  hipStream_t s = ctx.stream();
+  std::vector<uint64_t*> ptrs(outs.size());
+  for (size_t i = 0; i < outs.size(); ++i) {
+    outs[i].resize_ext(ctx, chain_index, static_cast<size_t>(map.num_limbs), s);
+    outs[i].set_scale(scale);
+    ptrs[i] = outs[i].data();
+  }
+  encode_raw(ctx, chain_index, true, dev_values, n_ / 2, 0, scale, outs.size(), nullptr, ptrs.data(), dev_overflow, s);
+}
+
+void PhantomCKKSEncoder::decode_device(const PhantomContext& ctx, const PhantomPlaintext& plain,
+                                       std::complex<double>* dev_out) const {
+  if (plain.chain_index() >= ctx.total_parm_size() ||
+      ctx.get_context_data(plain.chain_index()).coeff_modulus_size() != plain.coeff_modulus_size())
+    throw std::invalid_argument("plaintext is not in the Ql basis of its chain index");
+  decode_raw(ctx, plain.chain_index(), plain.data(), nullptr, plain.scale(), 1, dev_out, ctx.stream());
+}
+
+void PhantomCKKSEncoder::encode_on_device(const PhantomContext& ctx, const std::vector<std::complex<double>>& values,
+                                          double scale, PhantomPlaintext& out, size_t chain_index) const {
+  if (values.size() > n_ / 2) throw std::invalid_argument("values has invalid size");
+  hipStream_t s = ctx.stream();
+  DeviceBuffer<std::complex<double>> dv;
+  if (!values.empty()) dv.upload(values, s);
+  DeviceBuffer<int> flag(1, s);
+  PHX_CHECK(hipMemsetAsync(flag.get(), 0, sizeof(int), s));
+  encode_device(ctx, dv.get(), values.size(), scale, out, chain_index, flag.get());
+  if (flag.download(s)[0]) throw std::invalid_argument("encoded values are too large");
+}
+
+void PhantomCKKSEncoder::decode_on_device(const PhantomContext& ctx, const PhantomPlaintext& plain,
+                                          std::vector<std::complex<double>>& out) const {
+  hipStream_t s = ctx.stream();
+  DeviceBuffer<std::complex<double>> dv(n_ / 2, s);
+  decode_device(ctx, plain, dv.get());
+  out = dv.download(s);
 }
 
 }  // namespace phantom

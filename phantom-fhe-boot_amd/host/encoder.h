@@ -5,10 +5,17 @@
 // embedding and its inverse are evaluated on the host in double precision with one size-N
 // complex FFT each (the reference runs its special FFT on the GPU, src/fft.cu); coefficients
 // are rounded to integers, reduced into each RNS limb exactly and moved to NTT form on the GPU.
+//
+// The *_device / *_on_device members run the whole chain on the GPU instead (csrc/encode.h: FP64
+// embedding, round and split, CRT composition), stream-ordered and batched.  The host members
+// are unchanged and remain what the bootstrap's setup and the boot session call: the device
+// embedding follows the host FFT's butterfly order, but nothing pins the two paths to identical
+// bits, so switching those callers may change their plaintexts' low bits.
 #pragma once
 
 #include <complex>
 #include <cstdint>
+#include <span>
 #include <vector>
 
 #include "ciphertext.h"
@@ -71,6 +78,31 @@ class PhantomCKKSEncoder {
     return v;
   }
 
+  // ---- device encoder: values and results in device memory, enqueued on ctx.stream(), no host
+  // synchronisation.  `dev_overflow` (device int, may be null) is set non-zero when a value times
+  // the scale is not finite or reaches 2^1000; it is never cleared here.
+  // encode: `num_values` (<= slots, zero-padded) complex values -> plaintext in the Ql basis
+  void encode_device(const PhantomContext& ctx, const std::complex<double>* dev_values, size_t num_values,
+                     double scale, PhantomPlaintext& out, size_t chain_index = 1, int* dev_overflow = nullptr) const;
+  // encode_sparse: the values tile every block of sparse_slots() slots
+  void encode_sparse_device(const PhantomContext& ctx, const std::complex<double>* dev_values, size_t num_values,
+                            double scale, PhantomPlaintext& out, size_t chain_index = 1,
+                            int* dev_overflow = nullptr) const;
+  // encode_ext: Ql of `chain_index` followed by P
+  void encode_ext_device(const PhantomContext& ctx, const std::complex<double>* dev_values, size_t num_values,
+                         double scale, PhantomPlaintext& out, size_t chain_index, int* dev_overflow = nullptr) const;
+  // batched encode_ext: outs.size() x slot_count() values fill `outs` in shared launches
+  void encode_ext_device(const PhantomContext& ctx, const std::complex<double>* dev_values, double scale,
+                         std::span<PhantomPlaintext> outs, size_t chain_index, int* dev_overflow = nullptr) const;
+  // decode: slot_count() complex values to dev_out; the plaintext is not modified
+  void decode_device(const PhantomContext& ctx, const PhantomPlaintext& plain, std::complex<double>* dev_out) const;
+  // host-vector convenience forms computed on the GPU: upload, run, synchronise; encode throws
+  // std::invalid_argument("encoded values are too large") as the host path does
+  void encode_on_device(const PhantomContext& ctx, const std::vector<std::complex<double>>& values, double scale,
+                        PhantomPlaintext& out, size_t chain_index = 1) const;
+  void decode_on_device(const PhantomContext& ctx, const PhantomPlaintext& plain,
+                        std::vector<std::complex<double>>& out) const;
+
   // host-side maps, exposed for the bootstrap precomputation and tests
   // slots -> real coefficients (inverse canonical embedding, coefficients not scaled)
   std::vector<double> slots_to_coeffs(const std::vector<std::complex<double>>& values) const;
@@ -90,5 +122,27 @@ class PhantomCKKSEncoder {
   std::vector<uint32_t> slot_index_;             // (5^j mod 2n - 1) / 2 for j < n/2
   std::vector<uint32_t> brev_;
 };
+
+// The device encoder on raw pointers, shared by the members above and the C-ABI
+// (csrc/capi_encode.cpp).  Complex data is interleaved (re, im) doubles.  Arguments are checked
+// (std::invalid_argument) before anything is enqueued on `s`.
+// limbs of a plaintext at chain_index: its Ql basis, or Ql followed by P (upload_ext_async's layout)
+phx::LimbMap encode_limb_map(const PhantomContext& ctx, size_t chain_index, bool ext);
+// the embedding alone.  inverse: count x ns complex -> count x n reals (ns = sparse_slots or n/2,
+// the values tiling every block of ns slots); forward: count x n reals -> count x ns complex
+void embed_raw(const PhantomContext& ctx, bool forward, const void* in, void* out, size_t sparse_slots, size_t count,
+               hipStream_t s);
+// out [count][limbs][n] = round(coeffs * scale) mod q, coefficient or NTT form
+void round_rns_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const double* coeffs, double scale,
+                   size_t count, bool ntt_form, uint64_t* out, int* dev_overflow, hipStream_t s);
+// plaintexts (NTT form, Ql basis; `plain` contiguous or `plains` one pointer each) -> mul x centred integer
+void compose_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* plain, const uint64_t* const* plains,
+                 size_t count, double mul, double* coeffs, hipStream_t s);
+// values [count][num_values] -> plaintexts, written to `out` (contiguous) or to outs[p]
+void encode_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const std::complex<double>* values,
+                size_t num_values, size_t sparse_slots, double scale, size_t count, uint64_t* out,
+                uint64_t* const* outs, int* dev_overflow, hipStream_t s);
+void decode_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* plain, const uint64_t* const* plains,
+                double scale, size_t count, std::complex<double>* values, hipStream_t s);
 
 }  // namespace phantom

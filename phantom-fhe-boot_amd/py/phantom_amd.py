@@ -103,6 +103,11 @@ _SIGS = {
     "phantom_boot_run": (ctypes.c_int, [vp, vp, sz, sz, vp, sz, ctypes.c_int]),
     "phantom_boot_run_grouped": (ctypes.c_int, [vp, vp, sz, sz, vp, sz, ctypes.c_int, ctypes.c_int]),
     "phantom_boot_decrypt": (ctypes.c_int, [vp, vp, sz, vp]),
+    "phantom_ckks_embed": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, sz, sz, vp]),
+    "phantom_ckks_round_rns": (ctypes.c_int, [vp, sz, ctypes.c_int, vp, ctypes.c_double, sz, ctypes.c_int, vp, vp, vp]),
+    "phantom_ckks_compose": (ctypes.c_int, [vp, sz, vp, sz, vp, vp]),
+    "phantom_ckks_encode": (ctypes.c_int, [vp, sz, ctypes.c_int, vp, sz, sz, ctypes.c_double, sz, vp, vp, vp]),
+    "phantom_ckks_decode": (ctypes.c_int, [vp, sz, vp, ctypes.c_double, sz, vp, vp]),
 }
 
 _lib = None
@@ -193,6 +198,40 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+class Encoder:
+    """CKKS encode / decode on the device (phantom_ckks_*): every argument that names data is a
+    device pointer (e.g. a torch tensor's data_ptr()): slot values are complex128 (interleaved
+    re, im doubles), coefficients float64, plaintexts int64 / uint64 words [count][limbs][n].
+    Calls enqueue on `stream` and return; nothing is synchronised."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.n = ctx.n
+        self.slots = ctx.n // 2
+
+    def limbs(self, chain_index, ext=False):
+        """words of one plaintext at chain_index are limbs * n"""
+        return load().phantom_context_coeff_modulus_size(self.ctx.handle, chain_index) + (self.ctx.size_P if ext else 0)
+
+    def embed(self, forward, src, dst, stream, sparse_slots=0, count=1):
+        check(load().phantom_ckks_embed(self.ctx.handle, 1 if forward else 0, src, dst, sparse_slots, count, stream))
+
+    def round_rns(self, chain_index, coeffs, scale, out, stream, ext=False, count=1, ntt_form=True, overflow=None):
+        check(load().phantom_ckks_round_rns(self.ctx.handle, chain_index, 1 if ext else 0, coeffs, scale, count,
+                                            1 if ntt_form else 0, out, overflow, stream))
+
+    def compose(self, chain_index, plain, coeffs, stream, count=1):
+        check(load().phantom_ckks_compose(self.ctx.handle, chain_index, plain, count, coeffs, stream))
+
+    def encode(self, chain_index, values, num_values, scale, out, stream, ext=False, sparse_slots=0, count=1,
+               overflow=None):
+        check(load().phantom_ckks_encode(self.ctx.handle, chain_index, 1 if ext else 0, values, num_values,
+                                         sparse_slots, scale, count, out, overflow, stream))
+
+    def decode(self, chain_index, plain, scale, values, stream, count=1):
+        check(load().phantom_ckks_decode(self.ctx.handle, chain_index, plain, scale, count, values, stream))
 
 
 def ptr_array(ptrs):
