@@ -371,6 +371,55 @@ int phantom_ckks_encode(const phantom_context *ctx, size_t chain_index, int ext,
 int phantom_ckks_decode(const phantom_context *ctx, size_t chain_index, const uint64_t *plain, double scale,
                         size_t count, double *values, hipStream_t stream);
 
+/* ---- the bootstrap's linear-transform diagonals on the device (EvalBootstrapSetup's precompute,
+ * src/bootstrap.cu:181-560; this engine's slot-domain butterfly stages) --------------
+ * Diagonals are complex vectors of interleaved (re, im) doubles; a band is [D][ns] of them with D
+ * sorted offsets on ns slots.  The device entry points enqueue on `stream`; the small tables they
+ * need are uploaded before the first launch (one wait for `stream`).  ns not a power of two >= 2
+ * (or above N/2), a stage outside 1 .. log2 ns, a null pointer or a capacity too small return
+ * PHANTOM_ERR_INVALID_ARGUMENT before anything is enqueued.  Each *_host twin runs the host code of
+ * the setup (boot::stage / compose / lift_blocks and the pre-rotation) and returns the same layout. */
+/* offsets of compose(stage(s_k), .. compose(stage(s_1), I)) on ns slots: set arithmetic alone
+ * (each stage adds {0, +h, -h mod ns}, h = 2^(s-1)); sorted, *count of them (host only) */
+int phantom_ltprep_stage_offsets(size_t ns, const int *stages, size_t num_stages, int *offsets, size_t capacity,
+                                 size_t *count);
+/* the diagonals of that product (inverse: the stages of the inverse map, as CoeffToSlot uses them)
+ * to dev_out [count][ns]; dev_scratch holds capacity_diagonals x ns complex values like dev_out.
+ * Twiddles are the context's embedding roots; the values equal the host twin's. */
+int phantom_ltprep_stage_products(const phantom_context *ctx, size_t ns, int inverse, const int *stages,
+                                  size_t num_stages, double *dev_out, double *dev_scratch, size_t capacity_diagonals,
+                                  hipStream_t stream);
+int phantom_ltprep_stage_products_host(size_t ns, int inverse, const int *stages, size_t num_stages, double *out,
+                                       size_t capacity_diagonals);
+/* dev_flags [2 D] (cleared here): [2 i] = band[i] times the constant (when apply_const) has a
+ * non-zero entry at some r with r + offsets[i] < ns, [2 i + 1] = at some r with r + offsets[i] >= ns */
+int phantom_ltprep_presence(const double *dev_band, size_t ns, const int *offsets, size_t num_diagonals, double c_re,
+                            double c_im, int apply_const, int *dev_flags, hipStream_t stream);
+/* offsets on n slots of the block-periodic lift (ns < n: offset a where flags[2 i], a - ns mod n
+ * where flags[2 i + 1]; ns == n: a where either), sorted (host only) */
+int phantom_ltprep_lifted_offsets(const int *offsets, const int *flags, size_t num_diagonals, size_t ns, size_t n,
+                                  int *keys, size_t capacity, size_t *count);
+/* baby-step giant-step shape of a level with those offsets (host only):
+ * shape = {stride, center, D, g, b}; dim1 = 0 picks g */
+int phantom_ltprep_shape(size_t n, const int *keys, size_t num_keys, int stride, uint32_t dim1, int *shape);
+/* the level's slot vectors, ready for phantom_ckks_encode: constant (full complex multiply, when
+ * apply_const), lift to n slots (ns < n; mask 0 none, 1 the CoeffToSlot output mask {1, -i}, 2 the
+ * SlotToCoeff input mask {1, i}, period 2 ns), giant-step pre-rotation.  dev_out [num_keys][n] in
+ * slot order, slots_out[num_keys] (host) = each one's slot u, offset (u - center) stride. */
+int phantom_ltprep_finish(const double *dev_band, size_t ns, size_t n, const int *band_offsets, size_t num_band,
+                          const int *keys, size_t num_keys, const int *shape, double c_re, double c_im,
+                          int apply_const, int mask, double *dev_out, int *slots_out, hipStream_t stream);
+/* host twin of presence + lifted_offsets + shape + finish from a host band: *count diagonals,
+ * keys_out / slots_out [capacity], out [capacity][n] (may be NULL: structure only) */
+int phantom_ltprep_finish_host(const double *band, size_t ns, size_t n, const int *band_offsets, size_t num_band,
+                               double c_re, double c_im, int apply_const, int mask, int stride, uint32_t dim1,
+                               int *shape, int *keys_out, int *slots_out, size_t capacity, size_t *count, double *out);
+/* diagonals of a dense row-major slots x slots device matrix (ExtractShiftedDiagonal, src/util.cu:298-312):
+ * dev_out[k][p] = A[p][(p + k) mod slots] * scale, dev_flags[k] (cleared here) = diagonal k has a
+ * non-zero entry */
+int phantom_ltprep_dense_diagonals(const double *dev_A, size_t slots, double scale, double *dev_out, int *dev_flags,
+                                   hipStream_t stream);
+
 /* ---- bootstrapping sessions (bootstrapping/bootstrapping_example.cu:69-160; src/bootstrap.cu) ----
  * A session is the SimpleBootstrapExample set-up as one object: N = 2^log_n, Q = {60, depth x 59},
  * P = special x 60 (CoeffModulus::Create), scale 2^59, levelBudget {enc, dec}, num_slots slots
@@ -400,6 +449,12 @@ typedef struct phantom_boot_session phantom_boot_session;
 int phantom_boot_session_create(int log_n, int depth, int special, const uint32_t *level_budget, uint32_t num_slots,
                                 uint32_t num_iterations, uint32_t precision, const uint8_t *seed,
                                 phantom_boot_session **out);
+/* phantom_boot_session_create with a flags word: PHANTOM_BOOT_DEVICE_SETUP builds the
+ * linear-transform plaintexts on the device (FHECKKSRNS::UseDeviceSetup); unknown bits are refused */
+#define PHANTOM_BOOT_DEVICE_SETUP 1u
+int phantom_boot_session_create_opts(int log_n, int depth, int special, const uint32_t *level_budget,
+                                     uint32_t num_slots, uint32_t num_iterations, uint32_t precision,
+                                     const uint8_t *seed, uint32_t flags, phantom_boot_session **out);
 int phantom_boot_session_destroy(phantom_boot_session *s);
 /* encrypt `count` vectors of num_slots reals (values[count][num_slots]) at chain_index with that
  * level's FLEXIBLEAUTO scale; *ct_bytes = the size of one serialized ciphertext */

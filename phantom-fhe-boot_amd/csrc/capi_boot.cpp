@@ -144,8 +144,16 @@ int phantom_eval_mod_coefficients(uint32_t K, uint32_t double_angle_iterations, 
 int phantom_boot_session_create(int log_n, int depth, int special, const uint32_t* level_budget, uint32_t num_slots,
                                 uint32_t num_iterations, uint32_t precision, const uint8_t* seed,
                                 phantom_boot_session** out) {
+  return phantom_boot_session_create_opts(log_n, depth, special, level_budget, num_slots, num_iterations, precision,
+                                          seed, 0, out);
+}
+
+int phantom_boot_session_create_opts(int log_n, int depth, int special, const uint32_t* level_budget,
+                                     uint32_t num_slots, uint32_t num_iterations, uint32_t precision,
+                                     const uint8_t* seed, uint32_t flags, phantom_boot_session** out) {
   PHX_CAPI_GUARD({
     if (!level_budget || !seed || !out) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (flags & ~PHANTOM_BOOT_DEVICE_SETUP) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "unknown session flags");
     if (log_n < 10 || log_n > 17 || depth < 1 || special < 1) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "bad parameters");
     auto b = std::make_unique<phantom_boot_session>();
     const size_t N = size_t(1) << log_n;
@@ -169,6 +177,7 @@ int phantom_boot_session_create(int log_n, int depth, int special, const uint32_
     b->iterations = num_iterations ? num_iterations : 1;
     b->precision = precision;
     b->boot = std::make_unique<FHECKKSRNS>(*b->enc);
+    b->boot->UseDeviceSetup((flags & PHANTOM_BOOT_DEVICE_SETUP) != 0);
     b->boot->EvalBootstrapSetup(*b->ctx, {level_budget[0], level_budget[1]}, scale, b->sf, 0, b->slots);
     b->boot->EvalMultKeyGen(*b->sk, *b->ctx);
     b->boot->EvalBootstrapKeyGen(*b->sk, *b->ctx, b->slots);

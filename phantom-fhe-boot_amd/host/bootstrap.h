@@ -25,6 +25,7 @@
 #include "encoder.h"
 #include "keys.h"
 #include "../csrc/ckks.h"
+#include "../csrc/ltprep.h"
 
 namespace phantom {
 
@@ -48,6 +49,51 @@ cvec apply(const DiagMap& T, const cvec& v);
 std::vector<double> chebyshev_coefficients(double (*f)(double, const double*), const double* args, int degree);
 // the EvalMod target before the double-angle iterations: (2 pi)^(-2^-r) cos(2 pi (K y - 1/4) / 2^r)
 double scaled_cosine(double y, const double* args /* {K, r} */);
+
+// ---- the same maps on the device (csrc/ltprep.h), and the host pieces both paths share ----------
+// The baby-step giant-step shape of a level from its diagonal offsets on n ring slots (multiples
+// of `stride`; dim1 = 0: g^2 >= 2 D).
+struct LtShape {
+  int stride = 1, center = 0, D = 0, g = 1, b = 1;
+};
+LtShape lt_shape(const std::vector<int>& keys, size_t n, uint32_t dim1, int stride);
+// compose(stage(s_k), .. compose(stage(s_1), I)) on ns slots by set arithmetic alone (compose never
+// drops a key): the sorted offsets after every stage, and per stage the table phx::ltprep_stage
+// reads ([D_t][3] rows of the previous band, -1 = none), back to back in `src`.
+struct StagePlan {
+  size_t ns = 0;
+  std::vector<int> stages;
+  std::vector<std::vector<int>> keys;  // [stage][D_t]
+  std::vector<int32_t> src;
+  std::vector<size_t> src_at;  // [stage] first word of its table in src
+  size_t max_diagonals() const;
+  const std::vector<int>& offsets() const { return keys.back(); }
+};
+// throws std::invalid_argument unless ns is a power of two >= 2 and every 1 <= s <= log2 ns
+StagePlan plan_stages(size_t ns, const std::vector<int>& stages);
+// runs the plan's stages on `stream`, ping-pong between `first` (written by the first stage) and
+// `second` ([max_diagonals()][ns] complex each, device); dev_src = the plan's src words in device
+// memory; returns the buffer that holds the result [offsets().size()][ns]
+void* stage_products_device(const PhantomContext& cc, const StagePlan& plan, bool inverse, const int32_t* dev_src,
+                            void* first, void* second, hipStream_t stream);
+// the host's value of the same product
+DiagMap stage_products_host(const StagePlan& plan, bool inverse);
+// offsets on n slots of the block-periodic lift of diagonals `offsets` on ns slots, from the
+// presence flags of phx::ltprep_presence (ns == n: the offsets themselves)
+std::vector<int> lifted_keys(const std::vector<int>& offsets, const std::vector<int>& flags, size_t ns, size_t n);
+// the finish of one level on the host (the twin of phx::ltprep_finish): level constant, lift to n
+// slots with the optional out / in masks (mask: phx::kLtMask*), shape, pre-rotation.  Returns the
+// present diagonals in slot order: (slot u, offset on n slots, pre-rotated values [n]).
+struct FinishedDiagonal {
+  int slot = 0, key = 0;
+  cvec values;
+};
+// the rows phx::ltprep_finish reads for a level of `shape` whose present offsets on n slots are
+// `keys`, from a band on ns slots with offsets `band_offsets` (both sorted); returns each row's slot u
+std::vector<int> finish_rows(const LtShape& shape, size_t ns, size_t n, const std::vector<int>& band_offsets,
+                             const std::vector<int>& keys, std::vector<phx::LtFinishRow>& rows);
+std::vector<FinishedDiagonal> finish_host(DiagMap T, size_t ns, size_t n, std::complex<double> cf, bool apply_const,
+                                          int mask, uint32_t dim1, int stride, LtShape& shape);
 }  // namespace boot
 
 // device copies of the Chebyshev leaf constant tables, keyed by content (they depend only on
@@ -138,6 +184,10 @@ class FHECKKSRNS {
   std::vector<std::shared_ptr<PhantomPlaintext>> EvalLinearTransformPrecompute(
       const PhantomContext& cc, const std::vector<std::vector<std::complex<double>>>& A, double scale = 1,
       uint32_t L = 0) const;
+  // the same from a row-major (N/2) x (N/2) matrix of interleaved (re, im) doubles in device memory,
+  // read on cc.stream(); always built on the device
+  std::vector<std::shared_ptr<PhantomPlaintext>> EvalLinearTransformPrecompute(
+      const PhantomContext& cc, const std::complex<double>* dev_A, double scale = 1, uint32_t L = 0) const;
   // the two-matrix (sparse) form: declared by the reference without a definition either; throws
   std::vector<std::shared_ptr<PhantomPlaintext>> EvalLinearTransformPrecompute(
       const PhantomContext& cc, const std::vector<std::vector<std::complex<double>>>& A,
@@ -183,6 +233,13 @@ class FHECKKSRNS {
   static uint32_t GetBootstrapDepth(const std::vector<uint32_t>& levelBudget);
   static uint32_t GetBootstrapDepthTight(const std::vector<uint32_t>& levelBudget);
   void UseTightLevels(bool tight) { tight_levels_ = tight; }
+  // Build the linear-transform plaintexts on the device (csrc/ltprep.h stage products and finish,
+  // then the batched device encoder) instead of on host threads.  Off by default; read whenever
+  // plaintexts are built (EvalBootstrapSetup, a deferred encoding, the Eval*Precompute calls).  Level
+  // shapes, present diagonals and rotation indices are those of the host path; the diagonals'
+  // values are equal too, so the plaintexts differ only by the two encoders' rounding.
+  void UseDeviceSetup(bool on) { device_setup_ = on; }
+  bool device_setup() const { return device_setup_; }
   // rotations (slot offsets) whose keys a bootstrap with `numSlots` slots needs
   std::vector<int> rotation_indices(uint32_t numSlots = 0) const;
   // chain index of a bootstrap's output
@@ -258,6 +315,17 @@ class FHECKKSRNS {
   // the baby-step giant-step shape of a level from its diagonal map (n ring slots, offsets multiples
   // of `stride`; dim1 = 0: g^2 >= 2 D)
   static void lt_shape(LTLevel& lv, const boot::DiagMap& T, size_t n, uint32_t dim1, int stride);
+  // device setup: build_levels(encode = true) without host diagonals, and the tail every device
+  // path shares: band [.][ns] (device, offsets band_offsets) -> finish -> batched encode -> attach.
+  // `keys` are the level's present offsets on the ring's slots; lv's shape is set by the caller.
+  void build_levels_device(const PhantomContext& cc, bool encode_dir, const LevelArgs& args, uint32_t slots,
+                           std::vector<LTLevel>& out) const;
+  void encode_level_device(const PhantomContext& cc, LTLevel& lv, const void* band, size_t ns,
+                           const std::vector<int>& band_offsets, const std::vector<int>& keys,
+                           std::complex<double> cf, bool apply_const, int mask) const;
+  std::vector<std::shared_ptr<PhantomPlaintext>> dense_precompute_device(const PhantomContext& cc,
+                                                                         const std::complex<double>* dev_A,
+                                                                         double scale, uint32_t L) const;
   // encode a level's diagonals (pre-rotated by -g i stride) in the extended basis at lv.chain
   void encode_level(const PhantomContext& cc, LTLevel& lv, const boot::DiagMap& T) const;
   std::vector<int32_t> dir_rotations(uint32_t slots, uint32_t M, bool encode_dir) const;
@@ -280,6 +348,7 @@ class FHECKKSRNS {
   mutable std::mutex precom_mu_;  // deferred encodings
   uint32_t correction_ = 0;
   bool tight_levels_ = false;
+  bool device_setup_ = false;
   size_t raise_level_ = 0;  // the level ModRaise lands on (reference layout: the spare level)
   std::map<uint32_t, Precom> precom_;
   std::vector<double> cheb_;

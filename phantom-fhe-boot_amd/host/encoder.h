@@ -8,9 +8,9 @@
 //
 // The *_device / *_on_device members run the whole chain on the GPU instead (csrc/encode.h: FP64
 // embedding, round and split, CRT composition), stream-ordered and batched.  The host members
-// are unchanged and remain what the bootstrap's setup and the boot session call: the device
-// embedding follows the host FFT's butterfly order, but nothing pins the two paths to identical
-// bits, so switching those callers may change their plaintexts' low bits.
+// are unchanged and remain what the bootstrap's setup (unless FHECKKSRNS::UseDeviceSetup) and the
+// boot session call: the device embedding follows the host FFT's butterfly order, but nothing pins
+// the two paths to identical bits, so switching those callers may change their plaintexts' low bits.
 #pragma once
 
 #include <complex>

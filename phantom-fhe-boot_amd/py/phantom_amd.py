@@ -108,6 +108,21 @@ _SIGS = {
     "phantom_ckks_compose": (ctypes.c_int, [vp, sz, vp, sz, vp, vp]),
     "phantom_ckks_encode": (ctypes.c_int, [vp, sz, ctypes.c_int, vp, sz, sz, ctypes.c_double, sz, vp, vp, vp]),
     "phantom_ckks_decode": (ctypes.c_int, [vp, sz, vp, ctypes.c_double, sz, vp, vp]),
+    "phantom_ltprep_stage_offsets": (ctypes.c_int, [sz, vp, sz, vp, sz, ctypes.POINTER(sz)]),
+    "phantom_ltprep_stage_products": (ctypes.c_int, [vp, sz, ctypes.c_int, vp, sz, vp, vp, sz, vp]),
+    "phantom_ltprep_stage_products_host": (ctypes.c_int, [sz, ctypes.c_int, vp, sz, vp, sz]),
+    "phantom_ltprep_presence": (ctypes.c_int, [vp, sz, vp, sz, ctypes.c_double, ctypes.c_double, ctypes.c_int, vp, vp]),
+    "phantom_ltprep_lifted_offsets": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, sz, ctypes.POINTER(sz)]),
+    "phantom_ltprep_shape": (ctypes.c_int, [sz, vp, sz, ctypes.c_int, ctypes.c_uint32, vp]),
+    "phantom_ltprep_finish": (ctypes.c_int, [vp, sz, sz, vp, sz, vp, sz, vp, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    "phantom_ltprep_finish_host": (ctypes.c_int, [vp, sz, sz, vp, sz, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_uint32, vp, vp, vp, sz,
+                                                  ctypes.POINTER(sz), vp]),
+    "phantom_ltprep_dense_diagonals": (ctypes.c_int, [vp, sz, ctypes.c_double, vp, vp, vp]),
+    "phantom_boot_session_create_opts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32,
+                                                        ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32,
+                                                        ctypes.POINTER(vp)]),
 }
 
 _lib = None
@@ -234,6 +249,110 @@ class Encoder:
         check(load().phantom_ckks_decode(self.ctx.handle, chain_index, plain, scale, count, values, stream))
 
 
+def _i32(values):
+    import numpy as np
+    return np.ascontiguousarray(values, dtype=np.int32)
+
+
+class LtPrep:
+    """The bootstrap's linear-transform diagonals built on the device (phantom_ltprep_*), and their
+    host twins.  Device arguments are device pointers (complex128 data as interleaved doubles); offset
+    lists, flags and shapes are host sequences / numpy int32 arrays.  A shape is the numpy int32 array
+    [stride, center, D, g, b]."""
+
+    MASK_NONE, MASK_OUT, MASK_IN = 0, 1, 2
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.slots = ctx.n // 2
+
+    @staticmethod
+    def stage_offsets(ns, stages):
+        import numpy as np
+        st = _i32(stages)
+        out = np.zeros(max(int(ns), 1), dtype=np.int32)
+        cnt = sz(0)
+        check(load().phantom_ltprep_stage_offsets(ns, st.ctypes.data, len(st), out.ctypes.data, len(out),
+                                                  ctypes.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def stage_products(self, ns, inverse, stages, dev_out, dev_scratch, capacity, stream):
+        st = _i32(stages)
+        check(load().phantom_ltprep_stage_products(self.ctx.handle, ns, 1 if inverse else 0, st.ctypes.data, len(st),
+                                                   dev_out, dev_scratch, capacity, stream))
+
+    @staticmethod
+    def stage_products_host(ns, inverse, stages):
+        """(offsets, complex128 [D, ns]) of the host's boot::stage / boot::compose product"""
+        import numpy as np
+        st = _i32(stages)
+        off = LtPrep.stage_offsets(ns, stages)
+        out = np.zeros((len(off), ns), dtype=np.complex128)
+        check(load().phantom_ltprep_stage_products_host(ns, 1 if inverse else 0, st.ctypes.data, len(st),
+                                                        out.ctypes.data, len(off)))
+        return off, out
+
+    @staticmethod
+    def presence(dev_band, ns, offsets, dev_flags, stream, const=None):
+        off = _i32(offsets)
+        c = complex(const) if const is not None else 1 + 0j
+        check(load().phantom_ltprep_presence(dev_band, ns, off.ctypes.data, len(off), c.real, c.imag,
+                                             0 if const is None else 1, dev_flags, stream))
+
+    @staticmethod
+    def lifted_offsets(offsets, flags, ns, n):
+        import numpy as np
+        off, fl = _i32(offsets), _i32(flags)
+        out = np.zeros(2 * len(off) + 1, dtype=np.int32)
+        cnt = sz(0)
+        check(load().phantom_ltprep_lifted_offsets(off.ctypes.data, fl.ctypes.data, len(off), ns, n, out.ctypes.data,
+                                                   len(out), ctypes.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    @staticmethod
+    def shape(n, keys, stride, dim1=0):
+        import numpy as np
+        k = _i32(keys)
+        out = np.zeros(5, dtype=np.int32)
+        check(load().phantom_ltprep_shape(n, k.ctypes.data, len(k), stride, dim1, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def finish(dev_band, ns, n, band_offsets, keys, shape, dev_out, stream, const=None, mask=0):
+        """returns the slot u of each of the len(keys) output diagonals"""
+        import numpy as np
+        off, k, sh = _i32(band_offsets), _i32(keys), _i32(shape)
+        slots = np.zeros(max(len(k), 1), dtype=np.int32)
+        c = complex(const) if const is not None else 1 + 0j
+        check(load().phantom_ltprep_finish(dev_band, ns, n, off.ctypes.data, len(off), k.ctypes.data, len(k),
+                                           sh.ctypes.data, c.real, c.imag, 0 if const is None else 1, mask, dev_out,
+                                           slots.ctypes.data, stream))
+        return slots[:len(k)].copy()
+
+    @staticmethod
+    def finish_host(band, ns, n, band_offsets, stride, dim1=0, const=None, mask=0):
+        """(shape, keys, slots, complex128 [K, n]) from a host band [D, ns]"""
+        import numpy as np
+        b = np.ascontiguousarray(band, dtype=np.complex128)
+        off = _i32(band_offsets)
+        cap = 2 * len(off) + 1
+        sh = np.zeros(5, dtype=np.int32)
+        keys, slots = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        out = np.zeros((cap, n), dtype=np.complex128)
+        cnt = sz(0)
+        c = complex(const) if const is not None else 1 + 0j
+        check(load().phantom_ltprep_finish_host(b.ctypes.data, ns, n, off.ctypes.data, len(off), c.real, c.imag,
+                                                0 if const is None else 1, mask, stride, dim1, sh.ctypes.data,
+                                                keys.ctypes.data, slots.ctypes.data, cap, ctypes.byref(cnt),
+                                                out.ctypes.data))
+        K = cnt.value
+        return sh, keys[:K].copy(), slots[:K].copy(), out[:K].copy()
+
+    @staticmethod
+    def dense_diagonals(dev_A, slots, scale, dev_out, dev_flags, stream):
+        check(load().phantom_ltprep_dense_diagonals(dev_A, slots, scale, dev_out, dev_flags, stream))
+
+
 def ptr_array(ptrs):
     return (vp * len(ptrs))(*ptrs)
 
@@ -275,14 +394,16 @@ class BootSession:
     """Owning handle of a phantom_boot_session (the SimpleBootstrapExample set-up; C4/C5)."""
 
     def __init__(self, seed, log_n=16, depth=29, special=10, level_budget=(2, 2), num_slots=0, iterations=1,
-                 precision=0):
+                 precision=0, device_setup=False):
+        """device_setup: build the linear-transform plaintexts on the device (off by default)"""
         lib = load()
         assert len(seed) == 32
         self.seed = bytes(seed)
         lb = (ctypes.c_uint32 * 2)(*level_budget)
         h = vp()
-        check(lib.phantom_boot_session_create(log_n, depth, special, lb, num_slots, iterations, precision,
-                                              self.seed, ctypes.byref(h)))
+        check(lib.phantom_boot_session_create_opts(log_n, depth, special, lb, num_slots, iterations, precision,
+                                                   self.seed, 1 if device_setup else 0, ctypes.byref(h)))
+        self.device_setup = bool(device_setup)
         self.handle = h
         self.n = 1 << log_n
         self.slots = num_slots or self.n // 2
