@@ -9,7 +9,10 @@
 //          coefficient difference between corresponding plaintexts (bound 1 + 4 e_host scale, e_host =
 //          the host embedding's error on that level's diagonals against long double) and how many
 //          coefficients differ; a dense EvalLinearTransformPrecompute through the host path, the
-//          device path and the device-pointer overload; one bootstrap through each setup.
+//          device path and the device-pointer overload; one bootstrap through each setup.  Every
+//          level row and the dense row carry "hash": FNV-1a 64 fingerprints of the plaintext sets
+//          (slot, chain, scale bits and raw device words of each present plaintext), and one row
+//          that of rotation_indices: two builds compute the same setup iff these lines agree.
 //   time : wall-clock medians of the host setup, the device setup and the structure-only setup
 //          (precompute = false), each bracketed by hipDeviceSynchronize, and the pool's peak
 //          during a device setup (in all, and beyond the plaintexts the setup keeps).
@@ -22,6 +25,7 @@
 #include <complex>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <string>
 #include <vector>
@@ -112,6 +116,41 @@ static std::vector<uint64_t> ext_coefficients(const PhantomContext& ctx, const P
   return tmp.download(s);
 }
 
+// FNV-1a 64 of a plaintext set: for each present slot in order, the slot index, the chain index,
+// the scale's bit pattern and the plaintext's raw device words (a fingerprint to compare two builds by)
+struct Fnv {
+  uint64_t h = 0xcbf29ce484222325ull;
+  void eat(const void* p, size_t bytes) {
+    const unsigned char* c = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < bytes; ++i) h = (h ^ c[i]) * 0x100000001b3ull;
+  }
+  void word(uint64_t w) { eat(&w, sizeof(w)); }
+  std::string hex() const {
+    char buf[20];
+    std::snprintf(buf, sizeof(buf), "%016llx", static_cast<unsigned long long>(h));
+    return buf;
+  }
+};
+
+static std::string set_hash(const PhantomContext& ctx, const std::vector<std::shared_ptr<PhantomPlaintext>>& set) {
+  Fnv f;
+  std::vector<uint64_t> words;
+  PHX_CHECK(hipStreamSynchronize(ctx.stream()));  // the set's encodings are queued on the stream
+  for (size_t u = 0; u < set.size(); ++u) {
+    if (!set[u]) continue;
+    const double scale = set[u]->scale();
+    uint64_t bits;
+    std::memcpy(&bits, &scale, sizeof(bits));
+    f.word(u);
+    f.word(set[u]->chain_index());
+    f.word(bits);
+    words.resize(set[u]->coeff_modulus_size() * set[u]->poly_modulus_degree());
+    PHX_CHECK(hipMemcpy(words.data(), set[u]->data(), words.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    f.eat(words.data(), words.size() * sizeof(uint64_t));
+  }
+  return f.hex();
+}
+
 struct SetDiff {
   bool same_structure = true;  // sizes, which plaintexts exist, chain indices, scales
   double max_diff = 0;         // centred coefficient difference
@@ -151,25 +190,6 @@ static SetDiff compare(const PhantomContext& ctx, const std::vector<std::shared_
     }
   }
   return d;
-}
-
-// the stages of each level, as EvalBootstrapSetup groups them (CoeffToSlot: inverse stages top-down,
-// the larger groups first; SlotToCoeff: the mirror image)
-static std::vector<std::vector<int>> level_stages(int logslots, uint32_t budget_in, bool encode_dir) {
-  const int budget = static_cast<int>(std::clamp<uint32_t>(budget_in, 1, static_cast<uint32_t>(logslots)));
-  std::vector<int> sz(budget, logslots / budget);
-  for (int i = 0; i < logslots % budget; ++i) ++sz[i];
-  std::vector<int> order;
-  for (int s = 1; s <= logslots; ++s) order.push_back(s);
-  if (encode_dir) std::reverse(order.begin(), order.end());
-  else std::reverse(sz.begin(), sz.end());
-  std::vector<std::vector<int>> out;
-  size_t idx = 0;
-  for (int c : sz) {
-    out.emplace_back(order.begin() + idx, order.begin() + idx + c);
-    idx += c;
-  }
-  return out;
 }
 
 struct Params {
@@ -213,6 +233,11 @@ static int run_check(int log_n, uint32_t slots_in) {
         host.FindBootstrapRotationIndices(slots, M) == dev.FindBootstrapRotationIndices(slots, M) &&
             host.FindCoeffsToSlotsRotationIndices(slots, M) == dev.FindCoeffsToSlotsRotationIndices(slots, M) &&
             host.FindSlotsToCoeffsRotationIndices(slots, M) == dev.FindSlotsToCoeffsRotationIndices(slots, M));
+  {
+    Fnv f;
+    for (int r : host.rotation_indices(slots)) f.word(static_cast<uint64_t>(r));
+    std::printf("{\"hashes\": \"rotation_indices\", \"hash\": \"%s\"}\n", f.hex().c_str());
+  }
   check("output_chain_equal", host.output_chain_index(slots) == dev.output_chain_index(slots),
         "\"chain\": " + std::to_string(dev.output_chain_index(slots)));
 
@@ -233,20 +258,18 @@ static int run_check(int log_n, uint32_t slots_in) {
                         : b.EvalSlotsToCoeffsPrecompute(ctx, ksi, rot, sf, flag_i, constant, 0);
     };
     const PlainSet ph = sets(host), pd = sets(dev), ph2 = sets(host2);
-    const std::vector<std::vector<int>> stages = level_stages(logslots, P.budget[dir], encode_dir);
-    bool levels_ok = ph.size() == pd.size() && ph.size() == stages.size() && ph.size() == ph2.size();
+    // the levels as EvalBootstrapSetup plans them (SlotToCoeff: the mirror image of the split)
+    std::vector<int> sizes = boot::split_stages(logslots, P.budget[dir]);
+    if (!encode_dir) std::reverse(sizes.begin(), sizes.end());
+    const std::vector<boot::LevelSpec> specs = boot::plan_levels(slots, n, sizes, encode_dir);
+    bool levels_ok = ph.size() == pd.size() && ph.size() == specs.size() && ph.size() == ph2.size();
     for (size_t gi = 0; levels_ok && gi < ph.size(); ++gi) {
-      // the level's diagonals from the host twin: their embedding error, and the shape they imply
-      const boot::StagePlan plan = boot::plan_stages(slots, stages[gi]);
-      const bool scale_here = encode_dir ? gi == 0 : gi + 1 == ph.size();
-      int mask = phx::kLtMaskNone;
-      if (slots < n && encode_dir && gi + 1 == ph.size()) mask = phx::kLtMaskOut;
-      if (slots < n && !encode_dir && gi == 0) mask = phx::kLtMaskIn;
+      // the level's diagonals as the host setup forms them: their embedding error, and the shape they imply
+      const boot::LevelSpec& spec = specs[gi];
       boot::LtShape shape;
-      const int stride = 1 << (*std::min_element(stages[gi].begin(), stages[gi].end()) - 1);
-      const std::vector<boot::FinishedDiagonal> diags =
-          boot::finish_host(boot::stage_products_host(plan, encode_dir), slots, n,
-                            flag_i ? cplx(0.0, constant) : cplx(constant, 0.0), scale_here, mask, 0, stride, shape);
+      const std::vector<boot::FinishedDiagonal> diags = boot::finish_host(
+          boot::stage_products_host(boot::plan_stages(slots, spec.stages), encode_dir), slots, n,
+          flag_i ? cplx(0.0, constant) : cplx(constant, 0.0), spec.apply_const, spec.mask, 0, spec.stride, shape);
       double e_host = 0;
       for (const auto& d : diags) {
         const std::vector<long double> want = slots_to_coeffs_ld(d.values, N);
@@ -261,12 +284,14 @@ static int run_check(int log_n, uint32_t slots_in) {
       const double lvl_scale = sf.at(gi);  // chain 1 + gi
       const double bound = 1 + 4 * e_host * lvl_scale;
       const SetDiff hd = compare(ctx, ph[gi], pd[gi]), hh = compare(ctx, ph[gi], ph2[gi]);
-      char buf[512];
+      char buf[768];
       std::snprintf(buf, sizeof(buf),
                     "\"dir\": \"%s\", \"level\": %zu, \"D\": %zu, \"present\": %zu, \"max_diff\": %.1f, \"bound\": %.1f, "
-                    "\"e_host\": %.3e, \"differing\": %zu, \"coefficients\": %zu, \"host_vs_host_differing\": %zu",
+                    "\"e_host\": %.3e, \"differing\": %zu, \"coefficients\": %zu, \"host_vs_host_differing\": %zu, "
+                    "\"hash\": {\"host\": \"%s\", \"device\": \"%s\", \"host2\": \"%s\"}",
                     encode_dir ? "CoeffsToSlots" : "SlotsToCoeffs", gi, pd[gi].size(), present, hd.max_diff, bound,
-                    e_host, hd.differing, hd.coefficients, hh.differing);
+                    e_host, hd.differing, hd.coefficients, hh.differing, set_hash(ctx, ph[gi]).c_str(),
+                    set_hash(ctx, pd[gi]).c_str(), set_hash(ctx, ph2[gi]).c_str());
       check("level_shape_equal", hd.same_structure && twin_ok, buf);
       check("level_plaintexts_within_encoder_bound", hd.plaintexts == present && hd.max_diff <= bound, buf);
       check("host_setup_bit_identical", hh.same_structure && hh.differing == 0 && hh.plaintexts == present, buf);
@@ -301,9 +326,11 @@ static int run_check(int log_n, uint32_t slots_in) {
     }
     const double bound = 1 + 4 * e_host * sf.at(L);
     const SetDiff d1 = compare(ctx, th, td), d2 = compare(ctx, td, tp);
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), "\"diagonals\": %zu, \"max_diff\": %.1f, \"bound\": %.1f, \"differing\": %zu",
-                  d1.plaintexts, d1.max_diff, bound, d1.differing);
+    char buf[512];
+    std::snprintf(buf, sizeof(buf), "\"diagonals\": %zu, \"max_diff\": %.1f, \"bound\": %.1f, \"differing\": %zu, "
+                  "\"hash\": {\"host\": \"%s\", \"device\": \"%s\", \"device_pointer\": \"%s\"}",
+                  d1.plaintexts, d1.max_diff, bound, d1.differing, set_hash(ctx, th).c_str(), set_hash(ctx, td).c_str(),
+                  set_hash(ctx, tp).c_str());
     check("dense_device_vs_host", d1.same_structure && d1.plaintexts == ks.size() && d1.max_diff <= bound, buf);
     check("dense_device_pointer_equals_device_path", d2.same_structure && d2.plaintexts == ks.size() && d2.differing == 0);
   }

@@ -24,76 +24,16 @@
 #include "context.h"
 #include "encoder.h"
 #include "keys.h"
+#include "lt_levels.h"
 #include "../csrc/ckks.h"
-#include "../csrc/ltprep.h"
 
 namespace phantom {
 
 namespace boot {
-using cvec = std::vector<std::complex<double>>;
-// a slot-domain linear map as diagonals: (T v)[p] = sum_a diag_a[p] v[p + a]  (a mod slots)
-using DiagMap = std::map<int, cvec>;
-
-// stage s (1 <= s <= log2 slots) of U's factorisation, or its inverse
-DiagMap stage(size_t slots, int s, bool inverse);
-// A * B (B applied first)
-DiagMap compose(const DiagMap& A, const DiagMap& B, size_t slots);
-// a map T on n slots applied to every n-block of an S-slot vector independently (S a multiple of
-// n): each diagonal of T becomes the within-block offsets it really is, so the result is correct
-// on inputs that are not n-periodic.  out_mask (period 2n) scales output slot p, in_mask (period
-// 2n) input slot q; null = 1.
-DiagMap lift_blocks(const DiagMap& T, size_t n, size_t S, const cvec* out_mask, const cvec* in_mask);
-// apply a DiagMap to a vector (tests)
-cvec apply(const DiagMap& T, const cvec& v);
 // Chebyshev interpolation coefficients of f on [-1, 1] (p(y) = sum_k c_k T_k(y), c_0 not halved)
 std::vector<double> chebyshev_coefficients(double (*f)(double, const double*), const double* args, int degree);
 // the EvalMod target before the double-angle iterations: (2 pi)^(-2^-r) cos(2 pi (K y - 1/4) / 2^r)
 double scaled_cosine(double y, const double* args /* {K, r} */);
-
-// ---- the same maps on the device (csrc/ltprep.h), and the host pieces both paths share ----------
-// The baby-step giant-step shape of a level from its diagonal offsets on n ring slots (multiples
-// of `stride`; dim1 = 0: g^2 >= 2 D).
-struct LtShape {
-  int stride = 1, center = 0, D = 0, g = 1, b = 1;
-};
-LtShape lt_shape(const std::vector<int>& keys, size_t n, uint32_t dim1, int stride);
-// compose(stage(s_k), .. compose(stage(s_1), I)) on ns slots by set arithmetic alone (compose never
-// drops a key): the sorted offsets after every stage, and per stage the table phx::ltprep_stage
-// reads ([D_t][3] rows of the previous band, -1 = none), back to back in `src`.
-struct StagePlan {
-  size_t ns = 0;
-  std::vector<int> stages;
-  std::vector<std::vector<int>> keys;  // [stage][D_t]
-  std::vector<int32_t> src;
-  std::vector<size_t> src_at;  // [stage] first word of its table in src
-  size_t max_diagonals() const;
-  const std::vector<int>& offsets() const { return keys.back(); }
-};
-// throws std::invalid_argument unless ns is a power of two >= 2 and every 1 <= s <= log2 ns
-StagePlan plan_stages(size_t ns, const std::vector<int>& stages);
-// runs the plan's stages on `stream`, ping-pong between `first` (written by the first stage) and
-// `second` ([max_diagonals()][ns] complex each, device); dev_src = the plan's src words in device
-// memory; returns the buffer that holds the result [offsets().size()][ns]
-void* stage_products_device(const PhantomContext& cc, const StagePlan& plan, bool inverse, const int32_t* dev_src,
-                            void* first, void* second, hipStream_t stream);
-// the host's value of the same product
-DiagMap stage_products_host(const StagePlan& plan, bool inverse);
-// offsets on n slots of the block-periodic lift of diagonals `offsets` on ns slots, from the
-// presence flags of phx::ltprep_presence (ns == n: the offsets themselves)
-std::vector<int> lifted_keys(const std::vector<int>& offsets, const std::vector<int>& flags, size_t ns, size_t n);
-// the finish of one level on the host (the twin of phx::ltprep_finish): level constant, lift to n
-// slots with the optional out / in masks (mask: phx::kLtMask*), shape, pre-rotation.  Returns the
-// present diagonals in slot order: (slot u, offset on n slots, pre-rotated values [n]).
-struct FinishedDiagonal {
-  int slot = 0, key = 0;
-  cvec values;
-};
-// the rows phx::ltprep_finish reads for a level of `shape` whose present offsets on n slots are
-// `keys`, from a band on ns slots with offsets `band_offsets` (both sorted); returns each row's slot u
-std::vector<int> finish_rows(const LtShape& shape, size_t ns, size_t n, const std::vector<int>& band_offsets,
-                             const std::vector<int>& keys, std::vector<phx::LtFinishRow>& rows);
-std::vector<FinishedDiagonal> finish_host(DiagMap T, size_t ns, size_t n, std::complex<double> cf, bool apply_const,
-                                          int mask, uint32_t dim1, int stride, LtShape& shape);
 }  // namespace boot
 
 // device copies of the Chebyshev leaf constant tables, keyed by content (they depend only on
@@ -233,11 +173,13 @@ class FHECKKSRNS {
   static uint32_t GetBootstrapDepth(const std::vector<uint32_t>& levelBudget);
   static uint32_t GetBootstrapDepthTight(const std::vector<uint32_t>& levelBudget);
   void UseTightLevels(bool tight) { tight_levels_ = tight; }
-  // Build the linear-transform plaintexts on the device (csrc/ltprep.h stage products and finish,
-  // then the batched device encoder) instead of on host threads.  Off by default; read whenever
-  // plaintexts are built (EvalBootstrapSetup, a deferred encoding, the Eval*Precompute calls).  Level
-  // shapes, present diagonals and rotation indices are those of the host path; the diagonals'
-  // values are equal too, so the plaintexts differ only by the two encoders' rounding.
+  // The back end that builds the linear-transform plaintexts.  Both follow one plan (lt_levels.h:
+  // boot::plan_levels, boot::plan_stages, boot::lt_shape, boot::present_slots); the host back end
+  // (default) forms the diagonals and encodes them on host threads, the device back end with the
+  // csrc/ltprep.h kernels and the batched device encoder.  Read whenever plaintexts are built
+  // (EvalBootstrapSetup, a deferred encoding, the Eval*Precompute calls).  Level shapes, present
+  // diagonals and rotation indices are the same; the diagonals' values are equal too, so the
+  // plaintexts differ only by the two encoders' rounding.
   void UseDeviceSetup(bool on) { device_setup_ = on; }
   bool device_setup() const { return device_setup_; }
   // rotations (slot offsets) whose keys a bootstrap with `numSlots` slots needs
@@ -261,16 +203,13 @@ class FHECKKSRNS {
   static constexpr int kChebDegree = 88;      // bootstrap.cuh:232-255 (89 coefficients)
 
  private:
-  // one level of a linear transform: diagonals (u - center) * stride, u < D, evaluated as
-  // baby steps j < g (hoisted rotations) and giant steps i < b
-  struct LTLevel {
-    int stride = 1, center = 0, D = 0, g = 1, b = 1;
+  // one level of a linear transform: its shape, its chain index and its plaintexts
+  struct LTLevel : boot::LtShape {
     size_t chain = 1;
     std::vector<std::unique_ptr<PhantomPlaintext>> pts;  // [D], pre-rotated by -g i stride; null = zero
     DeviceBuffer<const uint64_t*> d_pts;                // [b][g] device pointer table (zero-padded)
     DeviceBuffer<uint64_t> zero;                        // the zero plaintext absent diagonals point at
   };
-  // the precomputation of one slot count (the reference's CKKSBootstrapPrecom)
   // the arguments of one direction's build_levels, kept for a deferred encoding
   struct LevelArgs {
     std::vector<int> sizes;
@@ -279,6 +218,7 @@ class FHECKKSRNS {
     uint32_t dim1 = 0;
     bool times_i = false;  // the constant is i * constant (EvalCoeffsToSlotsPrecompute's flag_i)
   };
+  // the precomputation of one slot count (the reference's CKKSBootstrapPrecom)
   struct Precom {
     uint32_t slots = 0;
     std::vector<LTLevel> enc, dec;
@@ -287,9 +227,29 @@ class FHECKKSRNS {
   };
   void setup(const PhantomContext& cc, const std::vector<uint32_t>& levelBudget, const std::vector<double>& sf,
              uint32_t correctionFactor, uint32_t slots, const std::vector<uint32_t>& dim1, bool precompute);
-  // encode = false: the levels' structure (g, b, stride, center, chain) without their plaintexts
+  // One direction's levels, from boot::plan_levels: per level the stage plan, then the products, the
+  // finish and the encoding on the host, or (UseDeviceSetup) on the device.  encode = false: the
+  // levels' structure (g, b, stride, center, chain) without their plaintexts, always from the host.
   void build_levels(const PhantomContext& cc, bool encode_dir, const LevelArgs& args, uint32_t slots,
                     std::vector<LTLevel>& out, bool encode) const;
+  // host back end: encode the diagonals of T (a finish_map result, or a dense matrix's) that lv's
+  // shape holds, pre-rotated by -g i stride, in the extended basis at lv.chain
+  void encode_level(const PhantomContext& cc, LTLevel& lv, const boot::DiagMap& T) const;
+  // device back end: one planned level's stage products, presence flags (sparse packing) and shape,
+  // and the tail every device path shares: band [.][ns] (device, offsets band_offsets) -> finish ->
+  // batched encode -> attach.  `keys` are the level's present offsets on the ring's slots; lv's
+  // shape is set by the caller.
+  void device_level(const PhantomContext& cc, const boot::StagePlan& plan, bool inverse, const boot::LevelSpec& spec,
+                    std::complex<double> cf, uint32_t dim1, LTLevel& lv) const;
+  void encode_level_device(const PhantomContext& cc, LTLevel& lv, const void* band, size_t ns,
+                           const std::vector<int>& band_offsets, const std::vector<int>& keys,
+                           std::complex<double> cf, bool apply_const, int mask) const;
+  std::vector<std::shared_ptr<PhantomPlaintext>> dense_precompute_device(const PhantomContext& cc,
+                                                                         const std::complex<double>* dev_A,
+                                                                         double scale, uint32_t L) const;
+  // the setup of `slots` slots, or std::invalid_argument("Precomputations for .. slots were not
+  // generated" + advice); the guard shows that the caller holds precom_mu_
+  Precom& held_precom(const std::lock_guard<std::mutex>& held, uint32_t slots, const char* advice) const;
   const Precom& precom(uint32_t numSlots, const PhantomContext& cc) const;
   PhantomCiphertext apply_level(const PhantomContext& cc, const PhantomCiphertext& ct, const LTLevel& lv) const;
   void level_babies(const PhantomContext& cc, const PhantomCiphertext& in, const LTLevel& lv, LevelWork& w,
@@ -312,22 +272,10 @@ class FHECKKSRNS {
                               const PhantomCiphertext& ct, const PhantomContext& cc, uint32_t numSlots,
                               bool encode_dir) const;
   void attach(const PhantomContext& cc, LTLevel& lv, const std::vector<std::shared_ptr<PhantomPlaintext>>& pts) const;
-  // the baby-step giant-step shape of a level from its diagonal map (n ring slots, offsets multiples
-  // of `stride`; dim1 = 0: g^2 >= 2 D)
-  static void lt_shape(LTLevel& lv, const boot::DiagMap& T, size_t n, uint32_t dim1, int stride);
-  // device setup: build_levels(encode = true) without host diagonals, and the tail every device
-  // path shares: band [.][ns] (device, offsets band_offsets) -> finish -> batched encode -> attach.
-  // `keys` are the level's present offsets on the ring's slots; lv's shape is set by the caller.
-  void build_levels_device(const PhantomContext& cc, bool encode_dir, const LevelArgs& args, uint32_t slots,
-                           std::vector<LTLevel>& out) const;
-  void encode_level_device(const PhantomContext& cc, LTLevel& lv, const void* band, size_t ns,
-                           const std::vector<int>& band_offsets, const std::vector<int>& keys,
-                           std::complex<double> cf, bool apply_const, int mask) const;
-  std::vector<std::shared_ptr<PhantomPlaintext>> dense_precompute_device(const PhantomContext& cc,
-                                                                         const std::complex<double>* dev_A,
-                                                                         double scale, uint32_t L) const;
-  // encode a level's diagonals (pre-rotated by -g i stride) in the extended basis at lv.chain
-  void encode_level(const PhantomContext& cc, LTLevel& lv, const boot::DiagMap& T) const;
+  // the dense transform's level at chain 1 + L: every offset 0 .. N/2 - 1 (stride 1)
+  static LTLevel dense_level(const PhantomContext& cc, uint32_t L);
+  // a level's plaintexts handed over to the caller
+  static std::vector<std::shared_ptr<PhantomPlaintext>> share_plaintexts(LTLevel& lv);
   std::vector<int32_t> dir_rotations(uint32_t slots, uint32_t M, bool encode_dir) const;
   PhantomCiphertext eval_mod(const PhantomCiphertext& ct, const PhantomContext& cc) const;
   // the series / double angle / EvalMod on several ciphertexts in lockstep (one level and scale):

@@ -48,6 +48,15 @@ def test_setup_example_check(args):
                   f"max {r['max_diff']} (bound {r['bound']})")
         if r["check"] == "host_setup_bit_identical":
             assert r["host_vs_host_differing"] == 0, r
+        if r["check"] in PER_LEVEL:  # the fingerprints another build's run is compared by
+            assert sorted(r["hash"]) == ["device", "host", "host2"], r
+            assert all(len(h) == 16 and int(h, 16) >= 0 for h in r["hash"].values()), r
+            assert r["hash"]["host"] == r["hash"]["host2"], r
+    dense = [r for r in checks if r["check"] == "dense_device_vs_host"][0]
+    assert sorted(dense["hash"]) == ["device", "device_pointer", "host"], dense
+    assert dense["hash"]["device"] == dense["hash"]["device_pointer"], dense
+    rot = [r for r in rows if r.get("hashes") == "rotation_indices"]
+    assert len(rot) == 1 and len(rot[0]["hash"]) == 16, rot
     boot = [r for r in checks if r["check"] == "bootstrap_precision"][0]
     print(f"avg_bits host {boot['avg_bits_host']} device {boot['avg_bits_device']}, outputs bit-identical: "
           f"{boot['outputs_bit_identical']}")
