@@ -224,6 +224,14 @@ __device__ __forceinline__ uint64_t split_reduce(uint64_t ll, uint64_t mm, uint6
 // value is L + H 2^60.  A 64-bit Barrett step on L and a Shoup product H (2^60 mod q), each in
 // [0, 4q) with approximate quotients, their sum below 8q < 2^63 and three carry-free conditional
 // subtractions: 15 multiplies instead of 30.  q < 2^60.
+// The 4q subtraction is needed over the stated input range (tests/test_arith_bounds.py holds
+// witnesses: H near 2^62 with a generic 2^60 mod q).  No sum that ks_rotate_batch_full forms is
+// known to need it.  a + b >= 4q takes a >= q together with b >= 2q.  r1 < 2^32 (q > 2^32), so the
+// approximate quotient of L drops only lo32(L) r1 / 2^64 < 2^-32 and a is the plain Barrett
+// remainder below 2q, at or above q only for residues below q L / 2^64.  b >= 2q needs the Shoup
+// quotient low (residues below q H / 2^64) with a dropped cross word, or both dropped words.  The
+// generated primes 2^60 - e (e < 2^21) have c60 = e and c60s < 2^26, one-word multipliers, so
+// b < q + 2^-6 q there; for limbs below 2^51, H < 2^44 makes a low Shoup quotient a 2^-20 event.
 __device__ __forceinline__ uint64_t split_reduce2(uint64_t ll, uint64_t mm, uint64_t hh, const SplitRed& k, uint64_t q,
                                                   uint64_t r1) {
   constexpr uint64_t kM30 = (1ull << 30) - 1;

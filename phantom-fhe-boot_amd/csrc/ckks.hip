@@ -462,9 +462,36 @@ __global__ __launch_bounds__(kBlock) void lin_comb_kernel(uint64_t* d, LimbScala
   }
 }
 
+// sum_k x_k c_k with x and c split in 30-bit halves: four 64-bit partial sums of FOLD products
+// each, folded into a 128-bit sum.  Below 2^60 the halves are below 2^30 and 16 products stay
+// below 2^64; a 61-bit modulus has high halves up to 2^31 (products up to 2^62) and only 4 fit
+// (as lt_bsgs_kernel's kChunk).
+template <int K, int FOLD>
+__device__ __forceinline__ u128 leaf_sum(const uint32_t (&xl)[K], const uint32_t (&xh)[K], const uint32_t* cl,
+                                         const uint32_t* ch) {
+  u128 acc{0, 0};
+#pragma unroll
+  for (int k0 = 0; k0 < K; k0 += FOLD) {
+    uint64_t ll = 0, m1 = 0, m2 = 0, hh = 0;
+#pragma unroll
+    for (int k = k0; k < K && k < k0 + FOLD; ++k) {
+      ll += static_cast<uint64_t>(xl[k]) * cl[k];
+      m1 += static_cast<uint64_t>(xl[k]) * ch[k];
+      m2 += static_cast<uint64_t>(xh[k]) * cl[k];
+      hh += static_cast<uint64_t>(xh[k]) * ch[k];
+    }
+    add128(acc, u128{ll, 0});
+    add128(acc, u128{m1 << 30, m1 >> 34});
+    add128(acc, u128{m2 << 30, m2 >> 34});
+    add128(acc, u128{hh << 60, hh >> 4});
+  }
+  return acc;
+}
+
 // blockIdx.y = limb l, blockIdx.x strides over the 2 n elements (t, k) of that limb.  The
 // limb's coefficients sit in LDS split into 30-bit halves; every output is sum_k x_k c_mk as
-// four 64-bit partial sums of 30-bit products (<= 16 terms: no overflow), one Barrett per output.
+// 64-bit partial sums of 30-bit products (leaf_sum: all <= 16 terms at once below 2^60, 4 at a
+// time for a 61-bit limb), one Barrett per output.
 template <int K>
 __global__ __launch_bounds__(kBlock) void leaf_combine_kernel(LeafArgs a, uint32_t log_n) {
   constexpr uint64_t kM30 = (1ull << 30) - 1;
@@ -481,6 +508,7 @@ __global__ __launch_bounds__(kBlock) void leaf_combine_kernel(LeafArgs a, uint32
   if (threadIdx.x < a.M) cadd[threadIdx.x] = a.cadd[static_cast<size_t>(threadIdx.x) * a.L + l];
   __syncthreads();
   const uint64_t q = a.q[l], r0 = a.barrett[2 * l], r1 = a.barrett[2 * l + 1];
+  const bool wide = (q >> 60) != 0;  // workgroup-uniform: the limb is blockIdx.y
   const size_t ln = static_cast<size_t>(a.L) << log_n;
   for (size_t e = blockIdx.x * (size_t)kBlock + threadIdx.x; e < 2 * n; e += (size_t)gridDim.x * kBlock) {
     const uint32_t t = e >= n ? 1 : 0;
@@ -493,19 +521,7 @@ __global__ __launch_bounds__(kBlock) void leaf_combine_kernel(LeafArgs a, uint32
       xh[k] = static_cast<uint32_t>(v >> 30);
     }
     for (int m = 0; m < a.M; ++m) {
-      uint64_t ll = 0, m1 = 0, m2 = 0, hh = 0;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const uint32_t cl = clo[m][k], ch = chi[m][k];
-        ll += static_cast<uint64_t>(xl[k]) * cl;
-        m1 += static_cast<uint64_t>(xl[k]) * ch;
-        m2 += static_cast<uint64_t>(xh[k]) * cl;
-        hh += static_cast<uint64_t>(xh[k]) * ch;
-      }
-      u128 acc{ll, 0};
-      add128(acc, u128{m1 << 30, m1 >> 34});
-      add128(acc, u128{m2 << 30, m2 >> 34});
-      add128(acc, u128{hh << 60, hh >> 4});
+      const u128 acc = wide ? leaf_sum<K, 4>(xl, xh, clo[m], chi[m]) : leaf_sum<K, 16>(xl, xh, clo[m], chi[m]);
       uint64_t v = barrett_reduce_128(acc, q, r0, r1);
       if (t == 0) v = add_mod(v, cadd[m], q);
       a.out[m][t * ln + el] = v;

@@ -102,7 +102,16 @@ struct BconvArgs {
   const uint64_t* mfma_rows = nullptr;   // [16 * ceil(obase / 16)][2] = {p_j, bits of double(1 / p_j)}
   const void* job_mfma_frag[kMaxJobs] = {};
   const uint64_t* job_mfma_rows[kMaxJobs] = {};
+  // how many products of 30-bit-split halves fit each of the four 64-bit partial sums (low x low,
+  // low x high, high x low, high x high): bconv_split_terms of the bases (16 for moduli below 2^60,
+  // 8 with 61-bit moduli on one side, 4 on both).  A larger ibase takes the 128-bit kernel instead
+  // of bconv_fixed_kernel.
+  int split_terms = 15;
 };
+// floor((2^64 - 1) / (mx * mc)) with mx = the largest half of an input below its ibase modulus (the
+// low half reaches 2^30 - 1, the high half (q - 1) >> 30) and mc likewise for a matrix entry below
+// its obase modulus: mx * mc bounds a term of every one of the four sums (host arrays)
+int bconv_split_terms(const uint64_t* ibase, int ibase_size, const uint64_t* obase, int obase_size);
 hipError_t bconv(const BconvArgs& a, size_t n, hipStream_t s);
 
 // Matrix-core base conversion tables.  The conversion y_j = sum_s t_s c_sj mod p_j runs as int8

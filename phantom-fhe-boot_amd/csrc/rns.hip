@@ -308,10 +308,15 @@ __global__ __launch_bounds__(kBlock) void bconv_kernel(BconvArgs a, uint32_t n, 
   bconv_outputs(a, tx, ty, a.ibase_size, n, 2 * i, bb.group);
 }
 
-// Fixed ibase <= 15: 30-bit limb splitting.  With t = th 2^30 + tl and c = ch 2^30 + cl (t, c <
-// 2^60), sum_s t_s c_s = HH 2^60 + (M1 + M2) 2^30 + LL where every partial sum of <= 15 products
-// of 30-bit halves stays below 2^64: 4 v_mad_u64_u32 per term and no carry chains (the 64x64
-// product + 128-bit accumulate form costs ~7 instructions per term plus register shuffles).
+// Fixed ibase <= 15: 30-bit limb splitting.  With t = th 2^30 + tl and c = ch 2^30 + cl,
+// sum_s t_s c_s = HH 2^60 + (M1 + M2) 2^30 + LL with four 64-bit partial sums (LL = sum tl cl,
+// M1 = sum tl ch, M2 = sum th cl, HH = sum th ch): 4 v_mad_u64_u32 per term and no carry chains
+// (the 64x64 product + 128-bit accumulate form costs ~7 instructions per term plus register
+// shuffles).  The low halves reach 2^30 - 1 whatever the moduli; the high halves stay below 2^30
+// for t, c < 2^60, and then 15 (even 16) products fit every sum.  A modulus of 2^60 or more on
+// either side has high halves up to 2^31, which enlarges HH and the cross sum of that side (M2 for
+// the inputs, M1 for the matrix): the sums then hold BconvArgs::split_terms products (8 with
+// 61-bit moduli on one side, 4 on both), and bconv() sends a larger ibase to bconv_kernel.
 template <int IB, bool PRE>
 __global__ __launch_bounds__(kBlock) void bconv_fixed_kernel(BconvArgs a, uint32_t n, uint32_t pairs) {
   static_assert(IB <= 15, "partial sums of 30-bit products must stay below 2^64");
@@ -1207,6 +1212,17 @@ void bconv_mfma_tables(const uint64_t* qhat_mod_p, const uint64_t* obase, int ib
   }
 }
 
+int bconv_split_terms(const uint64_t* ibase, int ibase_size, const uint64_t* obase, int obase_size) {
+  // the largest half on each side: a low half reaches 2^30 - 1 (the cross sums multiply it by
+  // the other side's high half), a high half (modulus - 1) >> 30
+  uint64_t hx = (uint64_t(1) << 30) - 1, hc = hx;
+  for (int i = 0; i < ibase_size; ++i) hx = std::max(hx, (ibase[i] - 1) >> 30);
+  for (int j = 0; j < obase_size; ++j) hc = std::max(hc, (obase[j] - 1) >> 30);
+  const unsigned __int128 prod = static_cast<unsigned __int128>(hx) * hc;
+  const unsigned __int128 terms = static_cast<unsigned __int128>(~uint64_t(0)) / prod;
+  return static_cast<int>(std::min<unsigned __int128>(terms, 1 << 20));
+}
+
 namespace {
 bool mfma_bconv_enabled() {
   static const bool on = [] {
@@ -1252,7 +1268,8 @@ hipError_t bconv(const BconvArgs& a, size_t n, hipStream_t s) {
   }
   const dim3 g(((pairs + kBlock - 1) / kBlock) * ((a.obase_size + kBconvJ - 1) / kBconvJ), 1, a.polys);
   const bool pre = a.qhat_inv != nullptr;
-  switch (a.ibase_size) {
+  // the fixed kernel's 64-bit partial sums hold split_terms products (61-bit moduli: fewer than 15)
+  switch (a.ibase_size <= a.split_terms ? a.ibase_size : 0) {
 #define PHX_BCONV_CASE(K)                                                                      \
   case K:                                                                                      \
     if (pre) bconv_fixed_kernel<K, true><<<g, kBlock, 0, s>>>(a, static_cast<uint32_t>(n), pairs); \

@@ -97,6 +97,7 @@ void DeviceBaseConverter::init(const std::vector<uint64_t>& in, const std::vecto
   d_qhat_inv.upload(qinv, s);
   d_qhat_inv_shoup.upload(qinvs, s);
   d_qhat_mod_p.upload(qhat, s);
+  split_terms = phx::bconv_split_terms(in.data(), (int)I, out.data(), (int)O);
   if (I <= (size_t)phx::kBconvMfmaMaxIbase && O <= (size_t)phx::kBconvMfmaMaxObase) {
     std::vector<uint8_t> frag(phx::bconv_mfma_frag_bytes((int)I, (int)O));
     std::vector<uint64_t> rows(2 * 16 * ((O + 15) / 16));
@@ -120,6 +121,7 @@ phx::BconvArgs DeviceBaseConverter::args(const uint64_t* in, uint64_t* out, bool
   a.obase_size = static_cast<int>(obase.size());
   a.mfma_frag = d_mfma_frag.get();
   a.mfma_rows = d_mfma_rows.get();
+  a.split_terms = split_terms;
   return a;
 }
 
@@ -128,6 +130,7 @@ RnsTool::RnsTool(size_t n, const std::vector<uint64_t>& qp, size_t size_P, size_
   if (size_Ql == 0 || size_Ql > size_Q_) throw std::invalid_argument("invalid level");
   base_Ql_.assign(qp.begin(), qp.begin() + size_Ql);
   base_P_.assign(qp.begin() + size_Q_, qp.end());
+  split_terms_ = phx::bconv_split_terms(qp.data(), (int)qp.size(), qp.data(), (int)qp.size());
   std::vector<uint64_t> bar(2 * size_Ql);
   for (size_t i = 0; i < size_Ql; ++i) barrett_ratio(base_Ql_[i], &bar[2 * i]);
   d_Ql_.upload(base_Ql_, s);
@@ -234,7 +237,8 @@ bool RnsTool::fused_bconv_ok(size_t ibase) const {
     const char* e = std::getenv("PHX_FUSED_BCONV");
     return e && e[0] == '1';
   }();
-  return on && n_ >= 1024 && ibase >= 1 && ibase <= 15;
+  // the prologue's 30-bit-split sums hold 15 products below 2^60, fewer with larger moduli
+  return on && n_ >= 1024 && ibase >= 1 && ibase <= 15 && ibase <= (size_t)split_terms_;
 }
 
 // every digit's conversion to its complement of QlP (digit b: t_cks limbs [b alpha, b alpha + part)
@@ -265,6 +269,7 @@ void RnsTool::digit_bconv(const uint64_t* t_cks, uint64_t* t_mod_up, hipStream_t
       a.job_obase_barrett[d] = c.d_obase_barrett.get();
       a.job_mfma_frag[d] = c.d_mfma_frag.get();
       a.job_mfma_rows[d] = c.d_mfma_rows.get();
+      a.split_terms = std::min(a.split_terms, c.split_terms);
     }
     hip_ok(phx::bconv(a, n_, s), "digit bconv");
   }

@@ -24,6 +24,7 @@ struct DeviceBaseConverter {
   // matrix-core form of the conversion (rns.h bconv_mfma_tables), empty when the shape has none
   DeviceBuffer<uint8_t> d_mfma_frag;
   DeviceBuffer<uint64_t> d_mfma_rows;
+  int split_terms = 15;  // phx::bconv_split_terms(ibase, obase)
   void init(const std::vector<uint64_t>& in, const std::vector<uint64_t>& out, hipStream_t s);
   phx::BconvArgs args(const uint64_t* in, uint64_t* out, bool prescale) const;
 };
@@ -115,6 +116,7 @@ class RnsTool {
   // the base conversion can run as the forward NTT's column-pass prologue (ntt.h BconvPrologue):
   // 2-D transform sizes and at most 15 input limbs; opt-in (PHX_FUSED_BCONV=1), see rns_tool.cpp
   bool fused_bconv_ok(size_t ibase) const;
+  int split_terms_ = 15;  // phx::bconv_split_terms over the whole chain (any converter's bases)
   // `count` batches: t_cks [count][Ql][n] -> t_mod_up [count][beta][QlP][n]
   void digit_bconv(const uint64_t* t_cks, uint64_t* t_mod_up, hipStream_t s, size_t count = 1) const;
   std::vector<DeviceBaseConverter> converters_;  // digit beta: part -> complement of QlP

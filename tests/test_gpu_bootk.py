@@ -74,9 +74,12 @@ def test_lt_bsgs(c4, rng, chain, g, b):
 
 @pytest.mark.parametrize("bits,g,b", [(61, 32, 8), (61, 16, 4), (61, 32, 3), (59, 32, 8)])
 def test_lt_bsgs_moduli(rng, bits, g, b):
-    """the inner sums' 30-bit split partial sums at their bounds: N = 4096, 8 + 2 moduli of `bits`
-    bits.  61-bit moduli make a high-half product reach 2^62, so the sums fold every 4 products
-    (LtArgs::q60 = 0); below 2^60 every 8 (tile kernel) or 16 (lt_bsgs_kernel).  == or_lt_bsgs"""
+    """the inner sums' 30-bit split partial sums over both kinds of moduli, with uniform random
+    operands: N = 4096, 8 + 2 moduli of `bits` bits.  61-bit moduli make a high-half product reach
+    2^62, so the sums fold every 4 products (LtArgs::q60 = 0); below 2^60 every 8 (tile kernel) or
+    16 (lt_bsgs_kernel).  == or_lt_bsgs.  Random residues sit near half of those bounds; the
+    operands that reach them (q - 1, low halves all ones, sums next to a multiple of q, the largest
+    60-bit primes) are in tests/test_gpu_edges.py."""
     n, size_p, chain = 1 << 12, 2, 1
     ctx = PA.Context(n, O.coeff_modulus_create(n, [bits] * 10), size_p)
     em = ctx.ql(chain) + ctx.moduli[ctx.size_Q:]
