@@ -476,6 +476,19 @@ int phantom_boot_run_grouped(phantom_boot_session *s, const uint8_t *dev_in, siz
                              uint8_t *dev_out, size_t out_stride, int lanes, int group);
 /* decrypt + decode one serialized ciphertext: the real parts of its num_slots slots */
 int phantom_boot_decrypt(phantom_boot_session *s, const uint8_t *dev_in, size_t capacity, double *values_out);
+/* phantom_boot_encrypt from DEVICE values [count][num_slots] interleaved complex, through the device
+ * encoder and one batched encryption (phantom_encrypt_symmetric_batch with the session's key): the
+ * same serialized byte format, header and metadata.  dev_values must be complete when the call is
+ * made; the call returns after the session's stream has written everything (one synchronisation). */
+int phantom_boot_encrypt_device(phantom_boot_session *s, const double *dev_values, size_t count, size_t chain_index,
+                                uint8_t *dev_out, size_t stride, size_t *ct_bytes);
+/* `count` serialized ciphertexts `stride` bytes apart, of one chain index, size and scale ->
+ * dev_values_out [count][num_slots] interleaved complex, decoded from the two leading limbs as
+ * phantom_boot_decrypt does.  The headers are validated on the host (one synchronisation); the
+ * values are written in the order of the session's stream: synchronise the device before another
+ * stream reads them or reuses dev_in. */
+int phantom_boot_decrypt_device(phantom_boot_session *s, const uint8_t *dev_in, size_t stride, size_t count,
+                                double *dev_values_out);
 
 /* ---- random sampling (src/prng.cu; seeds: include/prng.cuh:13-24) ---------------------
  * Every draw of key generation and encryption is ChaCha20 keystream (RFC 8439 block function,
@@ -500,6 +513,43 @@ int phantom_sample_uniform_seeded(const phantom_context *ctx, const uint8_t *see
 #define PHANTOM_SAMPLE_TERNARY 2
 int phantom_sample_poly(const phantom_context *ctx, int kind, const uint32_t *key, uint64_t nonce, uint64_t *out,
                         size_t coeff_modulus_size, hipStream_t stream);
+
+/* ---- batched symmetric encryption / decryption on the device (encrypt_symmetric_internal and
+ * ckks_decrypt, src/secretkey.cu:576-682, for a whole batch) ------------------------------------
+ * Values in device memory -> ciphertexts -> values in device memory with explicit key material: a
+ * fixed number of launches per internal chunk of ciphertexts, everything enqueued on `stream`,
+ * scratch from the engine's pool on that stream, no synchronisation.  Each result equals the
+ * one-at-a-time composition of the entries above bit for bit.  dev_sk is the secret in NTT form
+ * over rows 0 .. L-1 of the key-level chain ([>= L][N]).  Ciphertexts are [polys][L][N] words and
+ * start 16-byte aligned, an even number of words apart.  Bad arguments (a null pointer, count == 0,
+ * a chain index of 0 or past the end, limbs > ct_limbs, polys outside 2..3, a stride smaller than
+ * one ciphertext or odd, and whatever phantom_ckks_encode refuses) return
+ * PHANTOM_ERR_INVALID_ARGUMENT before any launch. */
+/* dev_out [count][N] small signed: e_p[k] = the centered binomial (PHANTOM_SAMPLE_CBD's value) of
+ * draw nonces[p] (host array) of the stream keyed by key[8] */
+int phantom_sample_cbd_small_batch(const phantom_context *ctx, const uint32_t *key, const uint64_t *nonces,
+                                   size_t count, int32_t *dev_out, hipStream_t stream);
+/* dev_values [count][num_values] complex (as phantom_ckks_encode) -> ciphertext p = (c0, c1), NTT form,
+ * at dev_out + p * out_stride words (0 = 2 L N): c1 = phantom_sample_uniform_seeded(seeds + 64 p),
+ * c0 = m - (c1 s + e) with e of draw nonces[p].  seeds [count][64] and nonces [count] are host arrays,
+ * read before the call returns.  dev_overflow as phantom_ckks_encode's. */
+int phantom_encrypt_symmetric_batch(const phantom_context *ctx, size_t chain_index, const uint64_t *dev_sk,
+                                    const double *dev_values, size_t num_values, size_t sparse_slots, double scale,
+                                    size_t count, const uint32_t *key, const uint64_t *nonces, const uint8_t *seeds,
+                                    uint64_t *dev_out, size_t out_stride, int *dev_overflow, hipStream_t stream);
+/* `count` ciphertexts of `polys` polynomials with ct_limbs limbs each, in_stride words apart (0 =
+ * polys ct_limbs N) -> dev_plain [count][limbs][N] = c0 + c1 s (+ c2 s^2), NTT form, over the
+ * leading limbs <= ct_limbs limbs (dropping limbs of a decryption is exact) */
+int phantom_decrypt_batch(const phantom_context *ctx, const uint64_t *dev_sk, const uint64_t *dev_in, size_t in_stride,
+                          size_t polys, size_t ct_limbs, size_t limbs, size_t count, uint64_t *dev_plain,
+                          hipStream_t stream);
+/* the same followed by phantom_ckks_decode over those limbs (limbs <= the data primes):
+ * dev_values [count][N/2] complex */
+int phantom_decrypt_decode_batch(const phantom_context *ctx, const uint64_t *dev_sk, const uint64_t *dev_in,
+                                 size_t in_stride, size_t polys, size_t ct_limbs, size_t limbs, size_t count,
+                                 double scale, double *dev_values, hipStream_t stream);
+/* host only: ciphertexts per internal chunk at this chain index */
+int phantom_encrypt_batch_chunk(const phantom_context *ctx, size_t chain_index, size_t *chunk);
 
 #ifdef __cplusplus
 }

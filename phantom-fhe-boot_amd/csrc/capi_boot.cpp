@@ -2,7 +2,9 @@
 // SimpleBootstrapExample set-up of bootstrapping/bootstrapping_example.cu:69-160 as one session
 // object, and batches of bootstraps over serialized ciphertexts held in device memory — the form
 // in which a multi-GPU job scatters its inputs and gathers its results (bench.py, config C5).
+#include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstring>
 #include <memory>
 #include <sstream>
@@ -232,6 +234,105 @@ int phantom_boot_encrypt(phantom_boot_session* s, const double* values, size_t c
       else b.enc->encode(*b.ctx, v, b.sf.at(chain_index - 1), pt, chain_index);
       PhantomCiphertext ct = b.sk->encrypt_symmetric(*b.ctx, pt);
       save_device(*b.ctx, ct, dev_out + i * stride, stride);
+    }
+    return PHANTOM_OK;
+  });
+}
+
+// Serialized words start at byte 58 of a slot, which is no 8-byte boundary: no kernel touches
+// them in place.  A chunk is encrypted into aligned pool scratch and moved with one strided copy
+// (the words of one ciphertext are contiguous after its header); the headers, all alike, follow
+// with one more.
+int phantom_boot_encrypt_device(phantom_boot_session* s, const double* dev_values, size_t count, size_t chain_index,
+                                uint8_t* dev_out, size_t stride, size_t* ct_bytes) {
+  PHX_CAPI_GUARD({
+    auto& b = session(s);
+    if (!dev_values || !dev_out || !ct_bytes) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (chain_index < 1 || chain_index > b.ctx->size_Q() - 1)
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "a bootstrap input needs at least two limbs");
+    const PhantomContext& ctx = *b.ctx;
+    const size_t n = ctx.poly_degree(), L = ctx.get_context_data(chain_index).coeff_modulus_size();
+    const size_t words = 2 * L * n, need = ser::kCiphertextHeaderBytes + words * 8;
+    *ct_bytes = need;
+    if (stride < need) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "stride smaller than one serialized ciphertext");
+    if (count == 0) return PHANTOM_OK;
+    const double scale = b.sf.at(chain_index - 1);  // FLEXIBLEAUTO: level l = chain index - 1 carries sf[l]
+    const size_t sparse = b.slots < n / 2 ? b.slots : 0;
+    hipStream_t st = ctx.stream();
+    const size_t chunk = encrypt_batch_chunk(ctx);
+    DeviceBuffer<uint64_t> stage(std::min(chunk, count) * words, st);
+    for (size_t p = 0; p < count; p += chunk) {
+      const size_t c = std::min(chunk, count - p);
+      b.sk->encrypt_symmetric_batch_to(ctx, reinterpret_cast<const std::complex<double>*>(dev_values) + p * b.slots,
+                                       b.slots, sparse, scale, chain_index, c, stage.get(), words);
+      PHX_CHECK(hipMemcpy2DAsync(dev_out + p * stride + ser::kCiphertextHeaderBytes, stride, stage.get(), words * 8,
+                                 words * 8, c, hipMemcpyDeviceToDevice, st));
+    }
+    ser::CiphertextHeader h;  // encrypt_symmetric's metadata
+    h.chain_index = chain_index;
+    h.size = 2;
+    h.poly_modulus_degree = n;
+    h.coeff_modulus_size = L;
+    h.scale = scale;
+    std::ostringstream os;
+    ser::write_ciphertext_header(os, h);
+    std::string hb;
+    for (size_t p = 0; p < count; ++p) hb += os.str();
+    PHX_CHECK(hipMemcpy2DAsync(dev_out, stride, hb.data(), ser::kCiphertextHeaderBytes, ser::kCiphertextHeaderBytes,
+                               count, hipMemcpyHostToDevice, st));
+    PHX_CHECK(hipStreamSynchronize(st));  // the header's host source is a temporary
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_boot_decrypt_device(phantom_boot_session* s, const uint8_t* dev_in, size_t stride, size_t count,
+                                double* dev_values_out) {
+  PHX_CAPI_GUARD({
+    auto& b = session(s);
+    if (!dev_in || !dev_values_out) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (count == 0) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "empty batch");
+    if (stride < ser::kCiphertextHeaderBytes) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "serialized ciphertext truncated");
+    const PhantomContext& ctx = *b.ctx;
+    hipStream_t st = ctx.stream();
+    // every header in one copy, validated on the host: the call's one synchronisation
+    std::vector<char> hb(count * ser::kCiphertextHeaderBytes);
+    PHX_CHECK(hipMemcpy2DAsync(hb.data(), ser::kCiphertextHeaderBytes, dev_in, stride, ser::kCiphertextHeaderBytes,
+                               count, hipMemcpyDeviceToHost, st));
+    PHX_CHECK(hipStreamSynchronize(st));
+    ser::CiphertextHeader h0;
+    for (size_t p = 0; p < count; ++p) {
+      std::istringstream is(std::string(hb.data() + p * ser::kCiphertextHeaderBytes, ser::kCiphertextHeaderBytes));
+      ser::CiphertextHeader h;
+      ser::read_ciphertext_header(is, h);
+      check_ciphertext_header(ctx, h);
+      if (h.words() > (stride - ser::kCiphertextHeaderBytes) / sizeof(uint64_t))
+        throw std::invalid_argument("serialized ciphertext truncated");
+      if (!h.is_ntt_form || h.chain_index < 1) throw std::invalid_argument("ciphertext is not a decryptable NTT-form level");
+      if (p == 0) h0 = h;
+      else if (h.chain_index != h0.chain_index || h.size != h0.size || h.scale != h0.scale)
+        throw std::invalid_argument("the ciphertexts of a batch must share chain index, size and scale");
+    }
+    // dropping limbs is exact (the plaintext is unchanged): only the two leading limbs of each
+    // polynomial are staged and decoded, as phantom_boot_decrypt decodes
+    const size_t n = ctx.poly_degree(), L = h0.coeff_modulus_size, polys = h0.size, limbs = std::min<size_t>(L, 2);
+    const size_t words = polys * limbs * n;
+    const size_t chunk = encrypt_batch_chunk(ctx);
+    const bool full = b.slots == n / 2;
+    DeviceBuffer<uint64_t> stage(std::min(chunk, count) * words, st);
+    DeviceBuffer<double> slots;
+    if (!full) slots.allocate(std::min(chunk, count) * n, st);
+    for (size_t p = 0; p < count; p += chunk) {
+      const size_t c = std::min(chunk, count - p);
+      for (size_t t = 0; t < polys; ++t)
+        PHX_CHECK(hipMemcpy2DAsync(stage.get() + t * limbs * n, words * 8,
+                                   dev_in + p * stride + ser::kCiphertextHeaderBytes + t * L * n * 8, stride,
+                                   limbs * n * 8, c, hipMemcpyDeviceToDevice, st));
+      double* vals = full ? dev_values_out + p * n : slots.get();
+      decrypt_decode_raw(ctx, b.sk->secret_key_array(), stage.get(), words, nullptr, polys, limbs, limbs, c, h0.scale,
+                         reinterpret_cast<std::complex<double>*>(vals), st);
+      if (!full)  // the first num_slots slots of each
+        PHX_CHECK(hipMemcpy2DAsync(dev_values_out + p * 2 * b.slots, b.slots * 16, vals, n * 8, b.slots * 16, c,
+                                   hipMemcpyDeviceToDevice, st));
     }
     return PHANTOM_OK;
   });

@@ -89,6 +89,12 @@ class PhantomCiphertext {
   const std::vector<uint8_t>& seed() const { return seed_; }
   // c1 must already hold the seed's expansion (synchronises stream `s`)
   void set_seed(std::vector<uint8_t> seed, hipStream_t s);
+  // the same with c1's fingerprint already on the host (8 coeff_modulus_size words: word i of it
+  // is c1 word i n / 8; encrypt_symmetric_batch gathers a whole batch's with one copy)
+  void set_seed(std::vector<uint8_t> seed, std::vector<uint64_t> fingerprint) {
+    seed_ = std::move(seed);
+    seed_fp_ = std::move(fingerprint);
+  }
   // hand the buffer to stream `s` (DeviceBuffer::set_stream): after a concurrent section, for a
   // result made on a side stream that the joining stream uses from now on
   void retag(hipStream_t s) { data_.set_stream(s); }

@@ -315,7 +315,7 @@ phx::LimbMap encode_limb_map(const PhantomContext& ctx, size_t chain_index, bool
   return m;
 }
 
-static void check_sparse(size_t n, size_t sparse_slots, size_t num_values) {
+void check_sparse(size_t n, size_t sparse_slots, size_t num_values) {
   const size_t ns = sparse_slots ? sparse_slots : n / 2;
   if (ns > n / 2 || (ns & (ns - 1))) throw std::invalid_argument("sparse slot count must be a power of two <= N/2");
   if (num_values > ns) throw std::invalid_argument("more values than slots");

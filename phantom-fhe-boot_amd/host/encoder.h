@@ -128,6 +128,8 @@ class PhantomCKKSEncoder {
 // (std::invalid_argument) before anything is enqueued on `s`.
 // limbs of a plaintext at chain_index: its Ql basis, or Ql followed by P (upload_ext_async's layout)
 phx::LimbMap encode_limb_map(const PhantomContext& ctx, size_t chain_index, bool ext);
+// throws unless sparse_slots (0 = n / 2) is a power of two <= n / 2 that holds num_values
+void check_sparse(size_t n, size_t sparse_slots, size_t num_values);
 // the embedding alone.  inverse: count x ns complex -> count x n reals (ns = sparse_slots or n/2,
 // the values tiling every block of ns slots); forward: count x n reals -> count x ns complex
 void embed_raw(const PhantomContext& ctx, bool forward, const void* in, void* out, size_t sparse_slots, size_t count,

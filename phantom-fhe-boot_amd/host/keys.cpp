@@ -7,6 +7,8 @@
 #include <string>
 
 #include "../csrc/ckks.h"
+#include "../csrc/encode.h"
+#include "../csrc/encrypt.h"
 #include "../csrc/ntt.h"
 #include "../csrc/rns.h"
 #include "evaluate.h"
@@ -403,6 +405,263 @@ void PhantomSecretKey::decrypt(const PhantomContext& ctx, const PhantomCiphertex
   if (ct.size() == 3)
     hip_ok(phx::poly_mul_add(ct.data() + 2 * L * n, s2_.get(), out.data(), out.data(), m, n, L, s), "+ c2 s^2");
   PHX_CHECK(hipStreamSynchronize(s));
+}
+
+// ---- batched symmetric encryption / decryption (csrc/encrypt.h) --------------------------------
+
+namespace {
+
+void batch_ok(hipError_t e, const char* what) {
+  if (e == hipErrorInvalidValue) throw std::invalid_argument(std::string(what) + ": unsupported shape or alignment");
+  if (e != hipSuccess) throw hip_error(e, what);
+}
+
+// the ciphertexts [p0, p0 + c) of a batch given as base + stride or as pointers
+phx::CtChunk chunk_of(const uint64_t* base, size_t stride, const uint64_t* const* ptrs, size_t p0, size_t c) {
+  phx::CtChunk k;
+  if (base) {
+    k.base = const_cast<uint64_t*>(base) + p0 * stride;
+    k.stride = stride;
+  } else {
+    for (size_t i = 0; i < c; ++i) k.ptr[i] = const_cast<uint64_t*>(ptrs[p0 + i]);
+  }
+  return k;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// count, the addresses (16-byte aligned: the kernels move two words per lane) and the stride of a
+// batch of `words`-word ciphertexts; returns the stride
+size_t check_batch(size_t count, const uint64_t* base, size_t stride, const uint64_t* const* ptrs, size_t words) {
+  if (count == 0) throw std::invalid_argument("empty batch");
+  if (!base && !ptrs) throw std::invalid_argument("null pointer");
+  if (stride == 0) stride = words;
+  if (base && (stride < words || stride % 2)) throw std::invalid_argument("stride smaller than one ciphertext, or odd");
+  if (base && !aligned16(base)) throw std::invalid_argument("ciphertexts must be 16-byte aligned");
+  if (!base)
+    for (size_t p = 0; p < count; ++p) {
+      if (!ptrs[p]) throw std::invalid_argument("null pointer");
+      if (!aligned16(ptrs[p])) throw std::invalid_argument("ciphertexts must be 16-byte aligned");
+    }
+  return stride;
+}
+
+// the key and the input batch of a decryption; returns the input stride
+size_t check_decrypt(const PhantomContext& ctx, const uint64_t* dev_sk, const uint64_t* in, size_t in_stride,
+                     const uint64_t* const* ins, size_t polys, size_t ct_limbs, size_t limbs, size_t count) {
+  if (polys < 2 || polys > 3) throw std::invalid_argument("unsupported ciphertext size");
+  if (limbs < 1 || limbs > ct_limbs || ct_limbs > ctx.size_QP()) throw std::invalid_argument("invalid limb count");
+  if (!dev_sk) throw std::invalid_argument("null pointer");
+  if (!aligned16(dev_sk)) throw std::invalid_argument("buffers must be 16-byte aligned");
+  return check_batch(count, in, in_stride, ins, polys * ct_limbs * ctx.poly_degree());
+}
+
+}  // namespace
+
+size_t encrypt_batch_chunk(const PhantomContext& ctx) { return phx::encrypt_chunk(ctx.poly_degree()); }
+
+void sample_cbd_small_raw(const PhantomContext& ctx, const phx::ChaChaKey& key, const uint64_t* nonces, size_t count,
+                          int32_t* dev_out, hipStream_t s) {
+  if (!nonces || !dev_out) throw std::invalid_argument("null pointer");
+  if (count == 0) throw std::invalid_argument("empty batch");
+  const size_t n = ctx.poly_degree();
+  for (size_t p = 0; p < count; p += phx::kCtChunkMax)
+    batch_ok(phx::sample_cbd_small(dev_out + p * n, n, key, nonces + p, std::min<size_t>(phx::kCtChunkMax, count - p), s),
+             "sample e");
+}
+
+void encrypt_symmetric_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* dev_sk,
+                           const std::complex<double>* values, size_t num_values, size_t sparse_slots, double scale,
+                           size_t count, const phx::ChaChaKey& key, const uint64_t* nonces, const uint8_t* seeds,
+                           uint64_t* out, size_t out_stride, uint64_t* const* outs, int* dev_overflow, hipStream_t s) {
+  if (!(scale > 0)) throw std::invalid_argument("scale must be positive");
+  const size_t n = ctx.poly_degree();
+  check_sparse(n, sparse_slots, num_values);
+  if (chain_index < 1 || chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  if (!dev_sk || !nonces || !seeds || (!values && num_values)) throw std::invalid_argument("null pointer");
+  if (!aligned16(dev_sk)) throw std::invalid_argument("buffers must be 16-byte aligned");
+  const size_t L = ctx.get_context_data(chain_index).coeff_modulus_size();
+  const size_t stride = check_batch(count, out, out_stride, outs, 2 * L * n);
+  const phx::EmbedTables et = ctx.embed_tables();
+  const phx::NttTables& ntt = ctx.gpu_rns_tables();
+  const phx::ModView m = ctx.mod_QP();
+  const phx::LimbMap map = phx::LimbMap::contiguous(static_cast<int>(L), 0);
+  const size_t chunk = encrypt_batch_chunk(ctx);
+  for (size_t p = 0; p < count; p += chunk) {
+    const size_t c = std::min(chunk, count - p);
+    const phx::CtChunk ct = chunk_of(out, stride, outs, p, c);
+    DeviceBuffer<double2> work(c * n, s);
+    DeviceBuffer<double> coeffs(c * n, s);
+    DeviceBuffer<int32_t> e(c * n, s);
+    batch_ok(phx::embed_inverse(et, reinterpret_cast<const double2*>(values) + p * num_values, num_values, sparse_slots,
+                                coeffs.get(), work.get(), c, s),
+             "embedding");
+    batch_ok(phx::sample_cbd_small(e.get(), n, key, nonces + p, c, s), "sample e");
+    batch_ok(phx::round_to_rns_minus(m, coeffs.get(), scale, e.get(), ct, n, L, c, dev_overflow, s), "round m - e");
+    if (out)
+      batch_ok(phx::ntt_forward(ntt, ct.base, ct.base, map.batched(static_cast<int>(c), stride, stride), s), "NTT(m - e)");
+    else
+      for (size_t i = 0; i < c; ++i) batch_ok(phx::ntt_forward(ntt, ct.ptr[i], ct.ptr[i], map, s), "NTT(m - e)");
+    batch_ok(phx::expand_and_finish(m, seeds + p * PhantomCiphertext::kSeedBytes, dev_sk, ct, n, L, c, s),
+             "a, m - e - a s");
+  }
+}
+
+void decrypt_raw(const PhantomContext& ctx, const uint64_t* dev_sk, const uint64_t* in, size_t in_stride,
+                 const uint64_t* const* ins, size_t polys, size_t ct_limbs, size_t limbs, size_t count,
+                 uint64_t* plain, hipStream_t s) {
+  if (!plain) throw std::invalid_argument("null pointer");
+  if (!aligned16(plain)) throw std::invalid_argument("buffers must be 16-byte aligned");
+  const size_t stride = check_decrypt(ctx, dev_sk, in, in_stride, ins, polys, ct_limbs, limbs, count);
+  const size_t n = ctx.poly_degree();
+  for (size_t p = 0; p < count; p += phx::kCtChunkMax) {
+    const size_t c = std::min<size_t>(phx::kCtChunkMax, count - p);
+    batch_ok(phx::decrypt_dot(ctx.mod_QP(), dev_sk, chunk_of(in, stride, ins, p, c), n, ct_limbs, polys, limbs, c,
+                              plain + p * limbs * n, s),
+             "c0 + c1 s");
+  }
+}
+
+void decrypt_decode_raw(const PhantomContext& ctx, const uint64_t* dev_sk, const uint64_t* in, size_t in_stride,
+                        const uint64_t* const* ins, size_t polys, size_t ct_limbs, size_t limbs, size_t count,
+                        double scale, std::complex<double>* values, hipStream_t s) {
+  if (!(scale > 0)) throw std::invalid_argument("scale must be positive");
+  if (limbs < 1 || limbs > ctx.size_Q()) throw std::invalid_argument("invalid limb count");
+  if (!values) throw std::invalid_argument("null pointer");
+  const size_t n = ctx.poly_degree(), decode_chain = ctx.size_Q() - limbs + 1;
+  const size_t chunk = encrypt_batch_chunk(ctx);
+  // everything is checked before the first chunk is enqueued
+  const size_t stride = check_decrypt(ctx, dev_sk, in, in_stride, ins, polys, ct_limbs, limbs, count);
+  for (size_t p = 0; p < count; p += chunk) {
+    const size_t c = std::min(chunk, count - p);
+    DeviceBuffer<uint64_t> plain(c * limbs * n, s);
+    decrypt_raw(ctx, dev_sk, in ? in + p * stride : nullptr, stride, ins ? ins + p : nullptr, polys, ct_limbs, limbs, c,
+                plain.get(), s);
+    decode_raw(ctx, decode_chain, plain.get(), nullptr, scale, c, values + p * (n / 2), s);
+  }
+}
+
+void PhantomSecretKey::encrypt_batch(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                     size_t num_values, size_t sparse_slots, double scale, size_t chain_index,
+                                     size_t count, uint64_t* out, size_t out_stride, uint64_t* const* outs,
+                                     std::vector<uint8_t>& seeds, int* dev_overflow) const {
+  // ciphertext p: one draw for its public seed, then one for e, as encrypt_symmetric draws them
+  seeds.resize(count * PhantomCiphertext::kSeedBytes);
+  std::vector<uint64_t> nonces(count);
+  const RandomStream before = enc_rng_;
+  for (size_t p = 0; p < count; ++p) {
+    enc_rng_.host_words(reinterpret_cast<uint64_t*>(seeds.data() + p * PhantomCiphertext::kSeedBytes),
+                        PhantomCiphertext::kSeedBytes / sizeof(uint64_t));
+    nonces[p] = enc_rng_.next_draw();
+  }
+  try {
+    encrypt_symmetric_raw(ctx, chain_index, s_.get(), dev_values, num_values, sparse_slots, scale, count,
+                          enc_rng_.key(), nonces.data(), seeds.data(), out, out_stride, outs, dev_overflow,
+                          ctx.stream());
+  } catch (const std::invalid_argument&) {
+    enc_rng_ = before;  // refused before any launch: no draw was used
+    throw;
+  }
+}
+
+void PhantomSecretKey::encrypt_symmetric_batch_to(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                                  size_t num_values, size_t sparse_slots, double scale,
+                                                  size_t chain_index, size_t count, uint64_t* dev_out,
+                                                  size_t out_stride, int* dev_overflow) const {
+  if (!dev_out) throw std::invalid_argument("null pointer");
+  std::vector<uint8_t> seeds;
+  encrypt_batch(ctx, dev_values, num_values, sparse_slots, scale, chain_index, count, dev_out, out_stride, nullptr,
+                seeds, dev_overflow);
+}
+
+void PhantomSecretKey::encrypt_to_ciphertexts(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                              size_t num_values, size_t sparse_slots, double scale,
+                                              size_t chain_index, std::span<PhantomCiphertext> outs,
+                                              int* dev_overflow) const {
+  if (outs.empty()) return;
+  if (chain_index < 1 || chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  const size_t n = ctx.poly_degree(), L = ctx.get_context_data(chain_index).coeff_modulus_size(), count = outs.size();
+  hipStream_t s = ctx.stream();
+  std::vector<uint64_t*> ptrs(count);
+  for (size_t p = 0; p < count; ++p) {
+    PhantomCiphertext& o = outs[p];
+    o.resize(ctx, chain_index, 2, s, false);
+    o.set_ntt_form(true);
+    o.set_scale(scale);
+    o.set_correction_factor(1);
+    o.SetNoiseScaleDeg(1);
+    o.set_asymmetric(false);
+    ptrs[p] = o.data();
+  }
+  std::vector<uint8_t> seeds;
+  encrypt_batch(ctx, dev_values, num_values, sparse_slots, scale, chain_index, count, nullptr, 0, ptrs.data(), seeds,
+                dev_overflow);
+  // every c1's fingerprint (PhantomCiphertext::set_seed) through one gather per chunk and one copy
+  const size_t fp_words = 8 * L;
+  DeviceBuffer<uint64_t> d_fp(count * fp_words, s);
+  for (size_t p = 0; p < count; p += phx::kCtChunkMax) {
+    const size_t c = std::min<size_t>(phx::kCtChunkMax, count - p);
+    batch_ok(phx::gather_c1_samples(chunk_of(nullptr, 0, ptrs.data(), p, c), n, L, c, d_fp.get() + p * fp_words, s),
+             "seed fingerprints");
+  }
+  const std::vector<uint64_t> fp = d_fp.download(s);  // the call's one synchronisation
+  for (size_t p = 0; p < count; ++p)
+    outs[p].set_seed(std::vector<uint8_t>(seeds.begin() + p * PhantomCiphertext::kSeedBytes,
+                                          seeds.begin() + (p + 1) * PhantomCiphertext::kSeedBytes),
+                     std::vector<uint64_t>(fp.begin() + p * fp_words, fp.begin() + (p + 1) * fp_words));
+}
+
+void PhantomSecretKey::encrypt_symmetric_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                               const std::complex<double>* dev_values, size_t num_values,
+                                               double scale, size_t chain_index, std::span<PhantomCiphertext> outs,
+                                               int* dev_overflow) const {
+  if (2 * encoder.slot_count() != ctx.poly_degree()) throw std::invalid_argument("encoder does not match the context");
+  encrypt_to_ciphertexts(ctx, dev_values, num_values, 0, scale, chain_index, outs, dev_overflow);
+}
+
+void PhantomSecretKey::encrypt_symmetric_sparse_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                                      const std::complex<double>* dev_values, size_t num_values,
+                                                      double scale, size_t chain_index,
+                                                      std::span<PhantomCiphertext> outs, int* dev_overflow) const {
+  if (2 * encoder.slot_count() != ctx.poly_degree()) throw std::invalid_argument("encoder does not match the context");
+  encrypt_to_ciphertexts(ctx, dev_values, num_values, encoder.sparse_slots(), scale, chain_index, outs, dev_overflow);
+}
+
+namespace {
+// chain index, size and scale shared by a batch; fills the data pointers
+void check_same_shape(std::span<const PhantomCiphertext> cts, std::vector<const uint64_t*>& ptrs) {
+  if (cts.empty()) throw std::invalid_argument("empty batch");
+  const PhantomCiphertext& f = cts[0];
+  if (f.size() < 2 || f.size() > 3) throw std::invalid_argument("unsupported ciphertext size");
+  ptrs.resize(cts.size());
+  for (size_t p = 0; p < cts.size(); ++p) {
+    const PhantomCiphertext& c = cts[p];
+    if (c.chain_index() != f.chain_index() || c.size() != f.size() || c.scale() != f.scale() ||
+        c.coeff_modulus_size() != f.coeff_modulus_size())
+      throw std::invalid_argument("the ciphertexts of a batch must share chain index, size and scale");
+    ptrs[p] = c.data();
+  }
+}
+}  // namespace
+
+void PhantomSecretKey::decrypt_batch(const PhantomContext& ctx, std::span<const PhantomCiphertext> cts,
+                                     size_t decode_limbs, uint64_t* dev_plain) const {
+  std::vector<const uint64_t*> ptrs;
+  check_same_shape(cts, ptrs);
+  const size_t L = cts[0].coeff_modulus_size();
+  decrypt_raw(ctx, s_.get(), nullptr, 0, ptrs.data(), cts[0].size(), L, decode_limbs ? decode_limbs : L, cts.size(),
+              dev_plain, ctx.stream());
+}
+
+void PhantomSecretKey::decrypt_decode_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                            std::span<const PhantomCiphertext> cts, size_t decode_limbs,
+                                            std::complex<double>* dev_values_out) const {
+  if (2 * encoder.slot_count() != ctx.poly_degree()) throw std::invalid_argument("encoder does not match the context");
+  std::vector<const uint64_t*> ptrs;
+  check_same_shape(cts, ptrs);
+  const size_t L = cts[0].coeff_modulus_size();
+  decrypt_decode_raw(ctx, s_.get(), nullptr, 0, ptrs.data(), cts[0].size(), L, decode_limbs ? decode_limbs : L,
+                     cts.size(), cts[0].scale(), dev_values_out, ctx.stream());
 }
 
 PhantomPublicKey PhantomSecretKey::gen_publickey(const PhantomContext& ctx) const {

@@ -13,16 +13,19 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <complex>
 #include <cstdint>
 #include <istream>
 #include <map>
 #include <memory>
 #include <ostream>
+#include <span>
 #include <vector>
 
 #include "buffer.h"
 #include "ciphertext.h"
 #include "context.h"
+#include "encoder.h"
 #include "random.h"
 
 namespace phantom {
@@ -165,6 +168,41 @@ class PhantomSecretKey {
     return p;
   }
 
+  // ---- batched, device to device (csrc/encrypt.h): values in device memory -> ciphertexts ->
+  // values in device memory, enqueued on ctx.stream() in a fixed number of launches per chunk of
+  // encrypt_batch_chunk ciphertexts (plus one NTT per ciphertext here, where every output owns its
+  // buffer; the raw forms below write one strided batch).
+  // encrypt_symmetric of outs.size() device-encoded plaintexts, plaintext p from the num_values
+  // (<= slots, zero-padded) complex values at dev_values + p * num_values.  Ciphertext p takes from
+  // this key's encryption stream one draw for its public seed, then one for its error: the draws of
+  // p successive encrypt_symmetric calls, so a for_testing key makes the same ciphertexts either
+  // way and no (seed, nonce) pair repeats.  Metadata and the recorded seed are encrypt_symmetric's.
+  // Synchronises the stream once (the seeds' fingerprints, gathered with one copy).
+  void encrypt_symmetric_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                               const std::complex<double>* dev_values, size_t num_values, double scale,
+                               size_t chain_index, std::span<PhantomCiphertext> outs,
+                               int* dev_overflow = nullptr) const;
+  // the same with the values tiling every block of encoder.sparse_slots() slots (encode_sparse_device)
+  void encrypt_symmetric_sparse_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                      const std::complex<double>* dev_values, size_t num_values, double scale,
+                                      size_t chain_index, std::span<PhantomCiphertext> outs,
+                                      int* dev_overflow = nullptr) const;
+  // the same draws into one strided device batch, ciphertext p ([2][L][n]) at dev_out + p * out_stride
+  // words (0 = 2 L n): no ciphertext objects, no recorded seeds and no synchronisation at all
+  void encrypt_symmetric_batch_to(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                  size_t num_values, size_t sparse_slots, double scale, size_t chain_index,
+                                  size_t count, uint64_t* dev_out, size_t out_stride,
+                                  int* dev_overflow = nullptr) const;
+  // decrypt of cts.size() ciphertexts that share chain index, size (2 or 3) and scale (else
+  // std::invalid_argument) over their leading decode_limbs limbs (0 = all; dropping limbs of a
+  // decryption is exact): dev_plain [count][limbs][n], NTT form.  No synchronisation.
+  void decrypt_batch(const PhantomContext& ctx, std::span<const PhantomCiphertext> cts, size_t decode_limbs,
+                     uint64_t* dev_plain) const;
+  // decrypt_batch followed by the device decoder: dev_values_out [count][slot_count] complex
+  void decrypt_decode_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                            std::span<const PhantomCiphertext> cts, size_t decode_limbs,
+                            std::complex<double>* dev_values_out) const;
+
   // kswitch key for new_key (NTT form over QP) -> enc_key (default s) (generate_one_kswitch_key)
   PhantomKSwitchKey make_kswitch_key(const PhantomContext& ctx, const uint64_t* new_key,
                                      const uint64_t* enc_key = nullptr);
@@ -173,6 +211,14 @@ class PhantomSecretKey {
   PhantomSecretKey(const PhantomContext& ctx, RandomStream rng, bool reproducible_encryption);
   PhantomSecretKey() = default;
   void init_powers(const PhantomContext& ctx);
+  // draws `count` (seed, error nonce) pairs from enc_rng_ and runs encrypt_symmetric_raw with them;
+  // `seeds` receives the count x 64 seed bytes
+  void encrypt_batch(const PhantomContext& ctx, const std::complex<double>* dev_values, size_t num_values,
+                     size_t sparse_slots, double scale, size_t chain_index, size_t count, uint64_t* out,
+                     size_t out_stride, uint64_t* const* outs, std::vector<uint8_t>& seeds, int* dev_overflow) const;
+  void encrypt_to_ciphertexts(const PhantomContext& ctx, const std::complex<double>* dev_values, size_t num_values,
+                              size_t sparse_slots, double scale, size_t chain_index,
+                              std::span<PhantomCiphertext> outs, int* dev_overflow) const;
   // symmetric encryption of zero over the first L limbs of Q u P under enc_key (default s):
   // (-(a s + e), a), NTT form
   // a_seed: take a from sample_uniform_seeded(a_seed) instead of this key's stream
@@ -202,5 +248,33 @@ void sample_uniform_seeded(const PhantomContext& ctx, const uint8_t* seed, uint6
 void sample_error_poly_ntt(const PhantomContext& ctx, RandomStream& rng, uint64_t* dst, size_t L);
 // ternary polynomial, returned in NTT form
 void sample_ternary_poly_ntt(const PhantomContext& ctx, RandomStream& rng, uint64_t* dst, size_t L);
+
+// Batched symmetric encryption / decryption on raw pointers with explicit key material, shared by
+// the members above and the C-ABI (csrc/capi_encrypt.cpp), in the manner of encode_raw / decode_raw
+// (encoder.h).  Arguments are checked (std::invalid_argument) before anything is enqueued on `s`;
+// nothing synchronises.  dev_sk: the secret in NTT form over key-chain rows 0 .. L-1 ([>= L][n]).
+// ciphertexts per internal chunk (csrc/encrypt.h encrypt_chunk); scratch stays below 64 MiB
+size_t encrypt_batch_chunk(const PhantomContext& ctx);
+// dev_out [count][n]: e[p] = the centered binomial of draw nonces[p] (host array) of stream `key`
+void sample_cbd_small_raw(const PhantomContext& ctx, const phx::ChaChaKey& key, const uint64_t* nonces, size_t count,
+                          int32_t* dev_out, hipStream_t s);
+// values [count][num_values] -> ciphertexts [2][L][n] (c0, c1) at chain_index, NTT form:
+// c1[p] = expansion of seeds[p] (host, 64 bytes each), c0[p] = m[p] - (c1[p] s + e[p]) with e[p] of
+// draw nonces[p] (host).  Ciphertext p at out + p * out_stride words (0 = 2 L n; even), or at outs[p].
+void encrypt_symmetric_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* dev_sk,
+                           const std::complex<double>* values, size_t num_values, size_t sparse_slots, double scale,
+                           size_t count, const phx::ChaChaKey& key, const uint64_t* nonces, const uint8_t* seeds,
+                           uint64_t* out, size_t out_stride, uint64_t* const* outs, int* dev_overflow, hipStream_t s);
+// ciphertexts of `polys` (2 or 3) polynomials with ct_limbs limbs, p at in + p * in_stride words
+// (0 = polys ct_limbs n) or at ins[p] -> plain [count][limbs][n] = c0 + c1 s (+ c2 s^2) over the
+// leading limbs <= ct_limbs limbs, NTT form
+void decrypt_raw(const PhantomContext& ctx, const uint64_t* dev_sk, const uint64_t* in, size_t in_stride,
+                 const uint64_t* const* ins, size_t polys, size_t ct_limbs, size_t limbs, size_t count,
+                 uint64_t* plain, hipStream_t s);
+// decrypt_raw followed by decode_raw at the chain index whose basis is those `limbs` limbs
+// (limbs <= size_Q): values [count][n / 2] complex
+void decrypt_decode_raw(const PhantomContext& ctx, const uint64_t* dev_sk, const uint64_t* in, size_t in_stride,
+                        const uint64_t* const* ins, size_t polys, size_t ct_limbs, size_t limbs, size_t count,
+                        double scale, std::complex<double>* values, hipStream_t s);
 
 }  // namespace phantom

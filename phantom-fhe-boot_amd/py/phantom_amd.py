@@ -123,6 +123,14 @@ _SIGS = {
     "phantom_boot_session_create_opts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32,
                                                         ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32,
                                                         ctypes.POINTER(vp)]),
+    "phantom_sample_cbd_small_batch": (ctypes.c_int, [vp, vp, vp, sz, vp, vp]),
+    "phantom_encrypt_symmetric_batch": (ctypes.c_int, [vp, sz, vp, vp, sz, sz, ctypes.c_double, sz, vp, vp, vp, vp, sz,
+                                                       vp, vp]),
+    "phantom_decrypt_batch": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp]),
+    "phantom_decrypt_decode_batch": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, sz, sz, ctypes.c_double, vp, vp]),
+    "phantom_encrypt_batch_chunk": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    "phantom_boot_encrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp, sz, ctypes.POINTER(sz)]),
+    "phantom_boot_decrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp]),
 }
 
 _lib = None
@@ -247,6 +255,50 @@ class Encoder:
 
     def decode(self, chain_index, plain, scale, values, stream, count=1):
         check(load().phantom_ckks_decode(self.ctx.handle, chain_index, plain, scale, count, values, stream))
+
+
+class Encryptor:
+    """Batched symmetric encryption / decryption on the device with explicit key material
+    (phantom_encrypt_symmetric_batch and friends).  dev_sk, values, ciphertexts and plaintexts are
+    device pointers; key (8 uint32 words), nonces (uint64 each) and seeds (64 bytes each) are host
+    data.  Calls enqueue on `stream` and return; nothing is synchronised."""
+
+    def __init__(self, ctx, dev_sk, key):
+        import numpy as np
+        self.ctx = ctx
+        self.dev_sk = dev_sk
+        self.key = np.ascontiguousarray(key, dtype=np.uint32)
+        assert self.key.size == 8
+
+    def chunk(self, chain_index):
+        c = sz(0)
+        check(load().phantom_encrypt_batch_chunk(self.ctx.handle, chain_index, ctypes.byref(c)))
+        return c.value
+
+    def sample_cbd_small(self, nonces, dev_out, stream):
+        import numpy as np
+        nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+        check(load().phantom_sample_cbd_small_batch(self.ctx.handle, self.key.ctypes.data, nn.ctypes.data, nn.size,
+                                                    dev_out, stream))
+
+    def encrypt(self, chain_index, values, num_values, scale, nonces, seeds, dev_out, stream, sparse_slots=0,
+                out_stride=0, overflow=None):
+        """seeds: bytes, 64 per ciphertext; len(nonces) ciphertexts"""
+        import numpy as np
+        nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+        seeds = bytes(seeds)
+        assert len(seeds) == 64 * nn.size
+        check(load().phantom_encrypt_symmetric_batch(self.ctx.handle, chain_index, self.dev_sk, values, num_values,
+                                                     sparse_slots, scale, nn.size, self.key.ctypes.data, nn.ctypes.data,
+                                                     seeds, dev_out, out_stride, overflow, stream))
+
+    def decrypt(self, dev_in, polys, ct_limbs, limbs, count, dev_plain, stream, in_stride=0):
+        check(load().phantom_decrypt_batch(self.ctx.handle, self.dev_sk, dev_in, in_stride, polys, ct_limbs, limbs,
+                                           count, dev_plain, stream))
+
+    def decrypt_decode(self, dev_in, polys, ct_limbs, limbs, count, scale, dev_values, stream, in_stride=0):
+        check(load().phantom_decrypt_decode_batch(self.ctx.handle, self.dev_sk, dev_in, in_stride, polys, ct_limbs,
+                                                  limbs, count, scale, dev_values, stream))
 
 
 def _i32(values):
@@ -444,6 +496,19 @@ class BootSession:
         out = np.zeros(self.slots, dtype=np.float64)
         check(load().phantom_boot_decrypt(self.handle, dev_ptr, capacity, out.ctypes.data))
         return out
+
+    def encrypt_device(self, dev_values, count, chain_index, dev_ptr, stride):
+        """dev_values: device complex128 [count, slots], complete when called; writes serialized
+        ciphertexts at dev_ptr + i * stride and returns the size of one."""
+        b = sz(0)
+        check(load().phantom_boot_encrypt_device(self.handle, dev_values, count, chain_index, dev_ptr, stride,
+                                                 ctypes.byref(b)))
+        return b.value
+
+    def decrypt_device(self, dev_ptr, stride, count, dev_values_out):
+        """`count` serialized ciphertexts -> device complex128 [count, slots], written in the order of
+        the session's stream: synchronise the device before reading them."""
+        check(load().phantom_boot_decrypt_device(self.handle, dev_ptr, stride, count, dev_values_out))
 
     def close(self):
         if self.handle:
