@@ -551,6 +551,34 @@ int phantom_decrypt_decode_batch(const phantom_context *ctx, const uint64_t *dev
 /* host only: ciphertexts per internal chunk at this chain index */
 int phantom_encrypt_batch_chunk(const phantom_context *ctx, size_t chain_index, size_t *chunk);
 
+/* ---- batched public-key encryption on the device (encrypt_zero_asymmetric_internal and
+ * encrypt_asymmetric, src/secretkey.cu:12-185, for a whole batch) ----------------------------------
+ * Values in device memory -> ciphertexts with explicit key material, under the conventions of the
+ * symmetric block above: a fixed number of launches per internal chunk, everything enqueued on
+ * `stream`, scratch from the engine's pool on that stream, no synchronisation.  Each result equals
+ * the one-at-a-time composition of the entries above bit for bit (phantom_sample_poly TERNARY / CBD
+ * over the whole key-level chain, phantom_nwt_forward_inplace, phantom_poly_op against the key,
+ * phantom_moddown_from_ntt, + phantom_ckks_encode), while only the L data rows and the special rows
+ * of the chain are ever formed.  dev_pk is the public key (-(a s + e), a) in NTT form over the whole
+ * key-level chain ([2][size_QP][N]), 16-byte aligned; the context needs at least one special prime.
+ * Bad arguments (those of the symmetric block, and a misaligned dev_pk) return
+ * PHANTOM_ERR_INVALID_ARGUMENT before any launch. */
+/* dev_out [count][N] small signed: the value of draw nonces[p] (host array) of the stream keyed by
+ * key[8], kind PHANTOM_SAMPLE_CBD (phantom_sample_cbd_small_batch's) or PHANTOM_SAMPLE_TERNARY */
+int phantom_sample_small_batch(const phantom_context *ctx, int kind, const uint32_t *key, const uint64_t *nonces,
+                               size_t count, int32_t *dev_out, hipStream_t stream);
+/* dev_values [count][num_values] complex (as phantom_ckks_encode) -> ciphertext p = (c0, c1), NTT form,
+ * at dev_out + p * out_stride words (0 = 2 L N): (pk0 u + e0, pk1 u + e1) divided by the special
+ * primes, + m on c0, with the ternary u and the centered binomial e0, e1 of the draws nonces[3 p],
+ * nonces[3 p + 1], nonces[3 p + 2].  nonces [count][3] is a host array, read before the call returns.
+ * dev_overflow as phantom_ckks_encode's. */
+int phantom_encrypt_asymmetric_batch(const phantom_context *ctx, size_t chain_index, const uint64_t *dev_pk,
+                                     const double *dev_values, size_t num_values, size_t sparse_slots, double scale,
+                                     size_t count, const uint32_t *key, const uint64_t *nonces, uint64_t *dev_out,
+                                     size_t out_stride, int *dev_overflow, hipStream_t stream);
+/* host only: ciphertexts per internal chunk at this chain index */
+int phantom_encrypt_asymmetric_batch_chunk(const phantom_context *ctx, size_t chain_index, size_t *chunk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
-// encrypt.hip — batched symmetric encryption / decryption kernels for gfx950 (see encrypt.h).
+// encrypt.hip — batched symmetric and public-key encryption / decryption kernels for gfx950 (see
+// encrypt.h).
 //
 // The kernels are streaming passes over [count][L][n] words with the chunk's ciphertexts in
 // grid y (or z): each lane moves 16 bytes per access (two residues, two coefficients) or, where a
@@ -200,6 +201,110 @@ dim3 pair_grid(size_t words, size_t count) {
   return dim3(static_cast<uint32_t>((words / 2 + kThreads - 1) / kThreads), static_cast<uint32_t>(count));
 }
 
+// ---- public-key encryption ---------------------------------------------------------------------
+struct DrawChunk {
+  uint64_t v[3 * kCtChunkMax];
+};
+
+// cbd_small_kernel over the draws of grid y, ternary where the kind says so
+__global__ void __launch_bounds__(kThreads)
+small_kernel(int32_t* __restrict__ out, uint32_t blocks, int kind, ChaChaKey key, DrawChunk nonces) {
+  const uint32_t b = blockIdx.x * kThreads + threadIdx.x;
+  if (b >= blocks) return;
+  const bool ternary = kind == kSmallTernary || (kind == kSmallAsym && blockIdx.y % 3 == 0);
+  uint32_t w[16];
+  chacha20_block(key, b, nonces.v[blockIdx.y], w);
+  int v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t r = chacha_word64(w, i);
+    v[i] = ternary ? static_cast<int>(r % 3) - 1 : __popcll(r & 0x1FFFFFull) - __popcll((r >> 21) & 0x1FFFFFull);
+  }
+  int4* o = reinterpret_cast<int4*>(out + (static_cast<size_t>(blockIdx.y) * blocks + b) * 8);
+  o[0] = make_int4(v[0], v[1], v[2], v[3]);
+  o[1] = make_int4(v[4], v[5], v[6], v[7]);
+}
+
+// v mod q, |v| < q
+__device__ __forceinline__ uint64_t signed_residue(int v, uint64_t q) {
+  return v >= 0 ? static_cast<uint64_t>(v) : q - static_cast<uint64_t>(-v);
+}
+
+// One lane: two coefficients of ciphertext z over the kRoundLimbs rows of grid y.  The rounding is
+// done once and serves every row; the three small samples are read as data.
+__global__ void __launch_bounds__(kThreads)
+round_lift_kernel(const uint64_t* __restrict__ modulus, const uint64_t* __restrict__ barrett, const AsymRows rw,
+                  const uint64_t* __restrict__ pmod, const double* __restrict__ coeffs, double scale,
+                  const int32_t* __restrict__ small, uint64_t* __restrict__ U, uint64_t* __restrict__ X, uint32_t n,
+                  int* overflow) {
+  const uint32_t k = 2 * (blockIdx.x * kThreads + threadIdx.x);
+  if (k >= n) return;
+  const size_t p = blockIdx.z;
+  const double2 x = *reinterpret_cast<const double2*>(coeffs + p * n + k);
+  const int32_t* sm = small + 3 * p * n + k;
+  const int2 u = *reinterpret_cast<const int2*>(sm);
+  const int2 e0 = *reinterpret_cast<const int2*>(sm + n);
+  const int2 e1 = *reinterpret_cast<const int2*>(sm + 2 * static_cast<size_t>(n));
+  const Rounded c0 = round_coeff(x.x * scale), c1 = round_coeff(x.y * scale);
+  if ((c0.bad || c1.bad) && overflow) *overflow = 1;
+  const int rows = rw.rows();
+  const int r0 = blockIdx.y * kRoundLimbs;
+  const int r1 = r0 + kRoundLimbs < rows ? r0 + kRoundLimbs : rows;
+  const size_t poly = static_cast<size_t>(rows) * n;
+  for (int r = r0; r < r1; ++r) {
+    const int t = rw.table_row(r);
+    const uint64_t q = modulus[t], b0 = barrett[2 * t], b1 = barrett[2 * t + 1];
+    const size_t at = static_cast<size_t>(r) * n + k;
+    uint64_t a0 = signed_residue(e0.x, q), a1 = signed_residue(e0.y, q);
+    if (r < rw.L) {
+      const uint64_t pq = pmod[r];
+      a0 = add_mod(a0, mul_mod(residue_minus(c0, 0, q, b0, b1), pq, q, b0, b1), q);
+      a1 = add_mod(a1, mul_mod(residue_minus(c1, 0, q, b0, b1), pq, q, b0, b1), q);
+    }
+    *reinterpret_cast<ulonglong2*>(U + p * poly + at) = make_ulonglong2(signed_residue(u.x, q), signed_residue(u.y, q));
+    *reinterpret_cast<ulonglong2*>(X + 2 * p * poly + at) = make_ulonglong2(a0, a1);
+    *reinterpret_cast<ulonglong2*>(X + (2 * p + 1) * poly + at) =
+        make_ulonglong2(signed_residue(e1.x, q), signed_residue(e1.y, q));
+  }
+}
+
+// One lane: two words of row r of ciphertext y, both products from one load of U
+__global__ void __launch_bounds__(kThreads)
+pk_fma_kernel(const uint64_t* __restrict__ modulus, const uint64_t* __restrict__ barrett, const AsymRows rw,
+              const uint64_t* __restrict__ pk, const uint64_t* __restrict__ U, uint64_t* __restrict__ X,
+              uint32_t log_n, size_t words) {
+  const size_t e = 2 * (blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x);
+  if (e >= words) return;
+  const int r = static_cast<int>(e >> log_n);
+  const int t = rw.table_row(r);
+  const uint64_t q = modulus[t], b0 = barrett[2 * t], b1 = barrett[2 * t + 1];
+  const size_t p = blockIdx.y;
+  const size_t key_at = (static_cast<size_t>(t) << log_n) + (e & ((size_t(1) << log_n) - 1));
+  const ulonglong2 u = *reinterpret_cast<const ulonglong2*>(U + p * words + e);
+  const ulonglong2 k0 = *reinterpret_cast<const ulonglong2*>(pk + key_at);
+  const ulonglong2 k1 = *reinterpret_cast<const ulonglong2*>(pk + (static_cast<size_t>(rw.total) << log_n) + key_at);
+  uint64_t* x0 = X + 2 * p * words + e;
+  uint64_t* x1 = x0 + words;
+  const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(x0);
+  const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(x1);
+  *reinterpret_cast<ulonglong2*>(x0) = make_ulonglong2(add_mod(a.x, mul_mod(u.x, k0.x, q, b0, b1), q),
+                                                       add_mod(a.y, mul_mod(u.y, k0.y, q, b0, b1), q));
+  *reinterpret_cast<ulonglong2*>(x1) = make_ulonglong2(add_mod(b.x, mul_mod(u.x, k1.x, q, b0, b1), q),
+                                                       add_mod(b.y, mul_mod(u.y, k1.y, q, b0, b1), q));
+}
+
+__global__ void __launch_bounds__(kThreads)
+scatter_ct_kernel(const uint64_t* __restrict__ src, const CtChunk ct, size_t words) {
+  const size_t e = 2 * (blockIdx.x * static_cast<size_t>(kThreads) + threadIdx.x);
+  if (e >= words) return;
+  *reinterpret_cast<ulonglong2*>(ct.at(blockIdx.y) + e) =
+      *reinterpret_cast<const ulonglong2*>(src + blockIdx.y * words + e);
+}
+
+bool rows_ok(const AsymRows& rw) {
+  return rw.L >= 1 && rw.alpha >= 1 && rw.first_p >= rw.L && rw.total == rw.first_p + rw.alpha && rw.total <= 0xffff;
+}
+
 }  // namespace
 
 hipError_t sample_cbd_small(int32_t* out, size_t n, const ChaChaKey& key, const uint64_t* nonces, size_t count,
@@ -246,6 +351,50 @@ hipError_t gather_c1_samples(const CtChunk& ct, size_t n, size_t L, size_t count
   const uint32_t per_ct = static_cast<uint32_t>(8 * L);
   hipLaunchKernelGGL(gather_c1_samples_kernel, dim3((per_ct + kThreads - 1) / kThreads, static_cast<uint32_t>(count)),
                      dim3(kThreads), 0, s, ct, static_cast<uint32_t>(n), per_ct, out);
+  return hipGetLastError();
+}
+
+hipError_t sample_small(int32_t* out, size_t n, SmallKind kind, const ChaChaKey& key, const uint64_t* nonces,
+                        size_t draws, hipStream_t s) {
+  if (!out || !nonces || !aligned16(out) || !degree_ok(n) || draws < 1 || draws > static_cast<size_t>(3 * kCtChunkMax) ||
+      kind < kSmallCbd || kind > kSmallAsym || (kind == kSmallAsym && draws % 3))
+    return hipErrorInvalidValue;
+  DrawChunk nc{};
+  for (size_t d = 0; d < draws; ++d) nc.v[d] = nonces[d];
+  const uint32_t blocks = static_cast<uint32_t>(n / 8);
+  hipLaunchKernelGGL(small_kernel, dim3((blocks + kThreads - 1) / kThreads, static_cast<uint32_t>(draws)),
+                     dim3(kThreads), 0, s, out, blocks, static_cast<int>(kind), key, nc);
+  return hipGetLastError();
+}
+
+hipError_t round_lift(ModView m, const AsymRows& rw, const uint64_t* pmod, const double* coeffs, double scale,
+                      const int32_t* small, uint64_t* U, uint64_t* X, size_t n, size_t count, int* overflow,
+                      hipStream_t s) {
+  if (!m.q || !m.barrett || !pmod || !coeffs || !small || !U || !X || !aligned16(coeffs) || !aligned16(small) ||
+      !aligned16(U) || !aligned16(X) || !degree_ok(n) || !rows_ok(rw) || count < 1 ||
+      count > static_cast<size_t>(kCtChunkMax))
+    return hipErrorInvalidValue;
+  const dim3 grid(static_cast<uint32_t>((n / 2 + kThreads - 1) / kThreads),
+                  static_cast<uint32_t>((rw.rows() + kRoundLimbs - 1) / kRoundLimbs), static_cast<uint32_t>(count));
+  hipLaunchKernelGGL(round_lift_kernel, grid, dim3(kThreads), 0, s, m.q, m.barrett, rw, pmod, coeffs, scale, small, U, X,
+                     static_cast<uint32_t>(n), overflow);
+  return hipGetLastError();
+}
+
+hipError_t pk_fma(ModView m, const AsymRows& rw, const uint64_t* pk, const uint64_t* U, uint64_t* X, size_t n,
+                  size_t count, hipStream_t s) {
+  if (!m.q || !m.barrett || !pk || !U || !X || !aligned16(pk) || !aligned16(U) || !aligned16(X) || !degree_ok(n) ||
+      !rows_ok(rw) || count < 1 || count > static_cast<size_t>(kCtChunkMax))
+    return hipErrorInvalidValue;
+  const size_t words = static_cast<size_t>(rw.rows()) * n;
+  hipLaunchKernelGGL(pk_fma_kernel, pair_grid(words, count), dim3(kThreads), 0, s, m.q, m.barrett, rw, pk, U, X,
+                     static_cast<uint32_t>(log2_of(n)), words);
+  return hipGetLastError();
+}
+
+hipError_t scatter_ct(const uint64_t* src, const CtChunk& ct, size_t words, size_t count, hipStream_t s) {
+  if (!src || !aligned16(src) || words < 2 || words % 2 || !chunk_ok(ct, count, words)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(scatter_ct_kernel, pair_grid(words, count), dim3(kThreads), 0, s, src, ct, words);
   return hipGetLastError();
 }
 

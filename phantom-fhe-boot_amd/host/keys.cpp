@@ -725,6 +725,149 @@ void PhantomPublicKey::encrypt_asymmetric(const PhantomContext& ctx, const Phant
   PHX_CHECK(hipStreamSynchronize(ctx.stream()));
 }
 
+// ---- batched public-key encryption (csrc/encrypt.h) --------------------------------------------
+
+size_t encrypt_asymmetric_batch_chunk(const PhantomContext& ctx, size_t chain_index) {
+  if (chain_index < 1 || chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  return phx::asym_chunk(ctx.poly_degree(), ctx.get_context_data(chain_index).coeff_modulus_size() + ctx.size_P());
+}
+
+void sample_small_raw(const PhantomContext& ctx, bool ternary, const phx::ChaChaKey& key, const uint64_t* nonces,
+                      size_t count, int32_t* dev_out, hipStream_t s) {
+  if (!nonces || !dev_out) throw std::invalid_argument("null pointer");
+  if (count == 0) throw std::invalid_argument("empty batch");
+  const size_t n = ctx.poly_degree(), step = 3 * phx::kCtChunkMax;
+  for (size_t p = 0; p < count; p += step)
+    batch_ok(phx::sample_small(dev_out + p * n, n, ternary ? phx::kSmallTernary : phx::kSmallCbd, key, nonces + p,
+                               std::min(step, count - p), s),
+             "sample small");
+}
+
+void encrypt_asymmetric_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* dev_pk,
+                            const std::complex<double>* values, size_t num_values, size_t sparse_slots, double scale,
+                            size_t count, const phx::ChaChaKey& key, const uint64_t* nonces, uint64_t* out,
+                            size_t out_stride, uint64_t* const* outs, int* dev_overflow, hipStream_t s) {
+  if (!(scale > 0)) throw std::invalid_argument("scale must be positive");
+  const size_t n = ctx.poly_degree();
+  check_sparse(n, sparse_slots, num_values);
+  if (chain_index < 1 || chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  if (ctx.size_P() == 0) throw std::invalid_argument("public-key encryption needs a special prime");
+  if (!dev_pk || !nonces || (!values && num_values)) throw std::invalid_argument("null pointer");
+  if (!aligned16(dev_pk)) throw std::invalid_argument("buffers must be 16-byte aligned");
+  const size_t L = ctx.get_context_data(chain_index).coeff_modulus_size();
+  const size_t ct_words = 2 * L * n;
+  const size_t stride = check_batch(count, out, out_stride, outs, ct_words);
+  const RnsTool& rt = ctx.get_context_data(chain_index).gpu_rns_tool();
+  const phx::EmbedTables et = ctx.embed_tables();
+  const phx::NttTables& ntt = ctx.gpu_rns_tables();
+  const phx::ModView m = ctx.mod_QP();
+  phx::AsymRows rw;
+  rw.L = static_cast<int>(L);
+  rw.alpha = static_cast<int>(ctx.size_P());
+  rw.first_p = static_cast<int>(ctx.size_Q());
+  rw.total = static_cast<int>(ctx.size_QP());
+  const size_t rows = L + ctx.size_P(), poly = rows * n;
+  phx::LimbMap map;
+  map.num_limbs = static_cast<int>(rows);
+  map.split = rw.L;
+  map.first_a = 0;
+  map.first_b = rw.first_p;
+  const bool direct = out && stride == ct_words;  // the division writes the batch in place
+  const size_t chunk = encrypt_asymmetric_batch_chunk(ctx, chain_index);
+  for (size_t p = 0; p < count; p += chunk) {
+    const size_t c = std::min(chunk, count - p);
+    DeviceBuffer<double2> work(c * n, s);
+    DeviceBuffer<double> coeffs(c * n, s);
+    DeviceBuffer<int32_t> small(3 * c * n, s);
+    DeviceBuffer<uint64_t> ux(3 * c * poly, s);  // U [c], then X [c][2]: 3 c polynomials of one shape
+    uint64_t* U = ux.get();
+    uint64_t* X = ux.get() + c * poly;
+    batch_ok(phx::embed_inverse(et, reinterpret_cast<const double2*>(values) + p * num_values, num_values, sparse_slots,
+                                coeffs.get(), work.get(), c, s),
+             "embedding");
+    batch_ok(phx::sample_asym_small(small.get(), n, key, nonces + 3 * p, c, s), "sample u, e0, e1");
+    batch_ok(phx::round_lift(m, rw, rt.bigP_mod_q(), coeffs.get(), scale, small.get(), U, X, n, c, dev_overflow, s),
+             "round and lift");
+    batch_ok(phx::ntt_forward(ntt, ux.get(), ux.get(), map.batched(static_cast<int>(3 * c)), s), "NTT(u, e0 + P m, e1)");
+    batch_ok(phx::pk_fma(m, rw, dev_pk, U, X, n, c, s), "pk u + e");
+    if (direct) {
+      rt.moddown_add(out + p * stride, X, false, ntt, s, 2 * c);
+    } else {
+      DeviceBuffer<uint64_t> stage(c * ct_words, s);
+      rt.moddown_add(stage.get(), X, false, ntt, s, 2 * c);
+      batch_ok(phx::scatter_ct(stage.get(), chunk_of(out, stride, outs, p, c), ct_words, c, s), "scatter");
+    }
+  }
+}
+
+void PhantomPublicKey::encrypt_batch(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                     size_t num_values, size_t sparse_slots, double scale, size_t chain_index,
+                                     size_t count, uint64_t* out, size_t out_stride, uint64_t* const* outs,
+                                     int* dev_overflow) {
+  if (pk_.size() != 2 || pk_.coeff_modulus_size() != ctx.size_QP())
+    throw std::invalid_argument("PhantomPublicKey has not been generated");
+  // ciphertext p: one draw each for u, e0 and e1, as encrypt_asymmetric draws them
+  std::vector<uint64_t> nonces(3 * count);
+  const RandomStream before = rng_;
+  for (uint64_t& v : nonces) v = rng_.next_draw();
+  try {
+    encrypt_asymmetric_raw(ctx, chain_index, pk_.data(), dev_values, num_values, sparse_slots, scale, count, rng_.key(),
+                           nonces.data(), out, out_stride, outs, dev_overflow, ctx.stream());
+  } catch (const std::invalid_argument&) {
+    rng_ = before;  // refused before any launch: no draw was used
+    throw;
+  }
+}
+
+void PhantomPublicKey::encrypt_asymmetric_batch_to(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                                   size_t num_values, size_t sparse_slots, double scale,
+                                                   size_t chain_index, size_t count, uint64_t* dev_out,
+                                                   size_t out_stride, int* dev_overflow) {
+  if (!dev_out) throw std::invalid_argument("null pointer");
+  encrypt_batch(ctx, dev_values, num_values, sparse_slots, scale, chain_index, count, dev_out, out_stride, nullptr,
+                dev_overflow);
+}
+
+void PhantomPublicKey::encrypt_to_ciphertexts(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                              size_t num_values, size_t sparse_slots, double scale,
+                                              size_t chain_index, std::span<PhantomCiphertext> outs,
+                                              int* dev_overflow) {
+  if (outs.empty()) return;
+  if (pk_.size() != 2 || pk_.coeff_modulus_size() != ctx.size_QP())
+    throw std::invalid_argument("PhantomPublicKey has not been generated");
+  if (chain_index < 1 || chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  hipStream_t s = ctx.stream();
+  std::vector<uint64_t*> ptrs(outs.size());
+  for (size_t p = 0; p < outs.size(); ++p) {
+    PhantomCiphertext& o = outs[p];
+    o.resize(ctx, chain_index, 2, s, false);  // drops a recorded seed
+    o.set_ntt_form(true);
+    o.set_scale(scale);
+    o.set_correction_factor(1);
+    o.SetNoiseScaleDeg(1);
+    o.set_asymmetric(true);
+    ptrs[p] = o.data();
+  }
+  encrypt_batch(ctx, dev_values, num_values, sparse_slots, scale, chain_index, outs.size(), nullptr, 0, ptrs.data(),
+                dev_overflow);
+}
+
+void PhantomPublicKey::encrypt_asymmetric_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                                const std::complex<double>* dev_values, size_t num_values,
+                                                double scale, size_t chain_index, std::span<PhantomCiphertext> outs,
+                                                int* dev_overflow) {
+  if (2 * encoder.slot_count() != ctx.poly_degree()) throw std::invalid_argument("encoder does not match the context");
+  encrypt_to_ciphertexts(ctx, dev_values, num_values, 0, scale, chain_index, outs, dev_overflow);
+}
+
+void PhantomPublicKey::encrypt_asymmetric_sparse_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                                       const std::complex<double>* dev_values, size_t num_values,
+                                                       double scale, size_t chain_index,
+                                                       std::span<PhantomCiphertext> outs, int* dev_overflow) {
+  if (2 * encoder.slot_count() != ctx.poly_degree()) throw std::invalid_argument("encoder does not match the context");
+  encrypt_to_ciphertexts(ctx, dev_values, num_values, encoder.sparse_slots(), scale, chain_index, outs, dev_overflow);
+}
+
 void PhantomPublicKey::save(std::ostream& os) const {
   if (pk_.size() != 2) throw std::invalid_argument("PhantomPublicKey has not been generated");
   pk_.save(os);

@@ -99,6 +99,28 @@ class PhantomPublicKey {
   // encrypt_zero_asymmetric (include/secretkey.h:78-84): an encryption of 0 at chain index 1
   PhantomCiphertext encrypt_zero_asymmetric(const PhantomContext& ctx);
 
+  // ---- batched, device to device (csrc/encrypt.h): encode + encrypt_asymmetric of outs.size()
+  // plaintexts, plaintext p from the num_values (<= slots, zero-padded) complex values at
+  // dev_values + p * num_values, enqueued on ctx.stream() in a fixed number of launches per chunk of
+  // encrypt_asymmetric_batch_chunk ciphertexts.  Ciphertext p takes three
+  // successive draws of this key's stream, for u, e0 and e1: the draws of p successive
+  // encrypt_asymmetric calls, so the key of a for_testing secret makes the same ciphertexts either
+  // way.  Metadata is encrypt_asymmetric's (no seed), and nothing synchronises.  A call refused with
+  // std::invalid_argument has launched nothing and used no draw.
+  void encrypt_asymmetric_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                const std::complex<double>* dev_values, size_t num_values, double scale,
+                                size_t chain_index, std::span<PhantomCiphertext> outs, int* dev_overflow = nullptr);
+  // the same with the values tiling every block of encoder.sparse_slots() slots
+  void encrypt_asymmetric_sparse_batch(const PhantomContext& ctx, const PhantomCKKSEncoder& encoder,
+                                       const std::complex<double>* dev_values, size_t num_values, double scale,
+                                       size_t chain_index, std::span<PhantomCiphertext> outs,
+                                       int* dev_overflow = nullptr);
+  // the same draws into one strided device batch, ciphertext p ([2][L][n]) at dev_out + p * out_stride
+  // words (0 = 2 L n)
+  void encrypt_asymmetric_batch_to(const PhantomContext& ctx, const std::complex<double>* dev_values,
+                                   size_t num_values, size_t sparse_slots, double scale, size_t chain_index,
+                                   size_t count, uint64_t* dev_out, size_t out_stride, int* dev_overflow = nullptr);
+
   // save / load (include/secretkey.h:86-101): the key-level ciphertext pk_.  A loaded key
   // encrypts with a fresh entropy-seeded stream.
   void save(std::ostream& os) const;
@@ -108,6 +130,13 @@ class PhantomPublicKey {
  private:
   friend class PhantomSecretKey;
   void encrypt_zero_raw(const PhantomContext& ctx, PhantomCiphertext& out, size_t chain_index);
+  // draws `count` (u, e0, e1) nonce triples from rng_ and runs encrypt_asymmetric_raw with them
+  void encrypt_batch(const PhantomContext& ctx, const std::complex<double>* dev_values, size_t num_values,
+                     size_t sparse_slots, double scale, size_t chain_index, size_t count, uint64_t* out,
+                     size_t out_stride, uint64_t* const* outs, int* dev_overflow);
+  void encrypt_to_ciphertexts(const PhantomContext& ctx, const std::complex<double>* dev_values, size_t num_values,
+                              size_t sparse_slots, double scale, size_t chain_index,
+                              std::span<PhantomCiphertext> outs, int* dev_overflow);
   PhantomCiphertext pk_;
   RandomStream rng_;
 };
@@ -265,6 +294,21 @@ void encrypt_symmetric_raw(const PhantomContext& ctx, size_t chain_index, const 
                            const std::complex<double>* values, size_t num_values, size_t sparse_slots, double scale,
                            size_t count, const phx::ChaChaKey& key, const uint64_t* nonces, const uint8_t* seeds,
                            uint64_t* out, size_t out_stride, uint64_t* const* outs, int* dev_overflow, hipStream_t s);
+// Batched public-key encryption (csrc/encrypt.h), checked and enqueued like encrypt_symmetric_raw.
+// ciphertexts per internal chunk at chain_index (csrc/encrypt.h asym_chunk: 256 MiB of scratch)
+size_t encrypt_asymmetric_batch_chunk(const PhantomContext& ctx, size_t chain_index);
+// dev_out [count][n]: the centered binomial (ternary = false) or the ternary value of draw nonces[p]
+// (host array) of stream `key`
+void sample_small_raw(const PhantomContext& ctx, bool ternary, const phx::ChaChaKey& key, const uint64_t* nonces,
+                      size_t count, int32_t* dev_out, hipStream_t s);
+// values [count][num_values] -> ciphertexts [2][L][n] at chain_index, NTT form:
+// (c0, c1)[p] = moddown(pk0 u + e0, pk1 u + e1) + (m[p], 0) with u, e0, e1 of the draws nonces[3 p],
+// nonces[3 p + 1], nonces[3 p + 2] (host).  dev_pk: the public key [2][size_QP][n], NTT form, 16-byte
+// aligned.  Ciphertext p at out + p * out_stride words (0 = 2 L n; even), or at outs[p].
+void encrypt_asymmetric_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* dev_pk,
+                            const std::complex<double>* values, size_t num_values, size_t sparse_slots, double scale,
+                            size_t count, const phx::ChaChaKey& key, const uint64_t* nonces, uint64_t* out,
+                            size_t out_stride, uint64_t* const* outs, int* dev_overflow, hipStream_t s);
 // ciphertexts of `polys` (2 or 3) polynomials with ct_limbs limbs, p at in + p * in_stride words
 // (0 = polys ct_limbs n) or at ins[p] -> plain [count][limbs][n] = c0 + c1 s (+ c2 s^2) over the
 // leading limbs <= ct_limbs limbs, NTT form

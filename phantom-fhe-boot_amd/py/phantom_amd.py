@@ -129,6 +129,10 @@ _SIGS = {
     "phantom_decrypt_batch": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp]),
     "phantom_decrypt_decode_batch": (ctypes.c_int, [vp, vp, vp, sz, sz, sz, sz, sz, ctypes.c_double, vp, vp]),
     "phantom_encrypt_batch_chunk": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+    "phantom_sample_small_batch": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, sz, vp, vp]),
+    "phantom_encrypt_asymmetric_batch": (ctypes.c_int, [vp, sz, vp, vp, sz, sz, ctypes.c_double, sz, vp, vp, vp, sz, vp,
+                                                        vp]),
+    "phantom_encrypt_asymmetric_batch_chunk": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
     "phantom_boot_encrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp, sz, ctypes.POINTER(sz)]),
     "phantom_boot_decrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp]),
 }
@@ -299,6 +303,43 @@ class Encryptor:
     def decrypt_decode(self, dev_in, polys, ct_limbs, limbs, count, scale, dev_values, stream, in_stride=0):
         check(load().phantom_decrypt_decode_batch(self.ctx.handle, self.dev_sk, dev_in, in_stride, polys, ct_limbs,
                                                   limbs, count, scale, dev_values, stream))
+
+
+class PublicEncryptor:
+    """Batched public-key encryption on the device with explicit key material
+    (phantom_encrypt_asymmetric_batch and friends).  dev_pk ([2][size_QP][n], NTT form), values and
+    ciphertexts are device pointers; key (8 uint32 words) and nonces (uint64 each, three per ciphertext:
+    u, e0, e1) are host data.  Calls enqueue on `stream` and return; nothing is synchronised."""
+
+    CBD, TERNARY = 1, 2
+
+    def __init__(self, ctx, dev_pk, key):
+        import numpy as np
+        self.ctx = ctx
+        self.dev_pk = dev_pk
+        self.key = np.ascontiguousarray(key, dtype=np.uint32)
+        assert self.key.size == 8
+
+    def chunk(self, chain_index):
+        c = sz(0)
+        check(load().phantom_encrypt_asymmetric_batch_chunk(self.ctx.handle, chain_index, ctypes.byref(c)))
+        return c.value
+
+    def sample_small(self, kind, nonces, dev_out, stream):
+        import numpy as np
+        nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+        check(load().phantom_sample_small_batch(self.ctx.handle, kind, self.key.ctypes.data, nn.ctypes.data, nn.size,
+                                                dev_out, stream))
+
+    def encrypt(self, chain_index, values, num_values, scale, nonces, dev_out, stream, sparse_slots=0, out_stride=0,
+                overflow=None):
+        """nonces: three per ciphertext (u, e0, e1); len(nonces) / 3 ciphertexts"""
+        import numpy as np
+        nn = np.ascontiguousarray(nonces, dtype=np.uint64).reshape(-1)
+        assert nn.size % 3 == 0
+        check(load().phantom_encrypt_asymmetric_batch(self.ctx.handle, chain_index, self.dev_pk, values, num_values,
+                                                      sparse_slots, scale, nn.size // 3, self.key.ctypes.data,
+                                                      nn.ctypes.data, dev_out, out_stride, overflow, stream))
 
 
 def _i32(values):
