@@ -288,6 +288,52 @@ int phantom_leaf_combine(const phantom_context *ctx, size_t chain_index, const u
                          const size_t *in_stride, size_t K, const uint64_t *coef, const uint64_t *cadd,
                          uint64_t *const *out, size_t M, hipStream_t stream);
 
+/* ---- hoisted encrypted 2-D convolution (DNN::Conv, src/dnn.cu:82-150) --------------------------
+ * A tensor is one ciphertext per channel: a width x width image sparse-packed in ns = Lg^2 slots,
+ * Lg = width 2^slotstr, pixel (r, c) at slot (r Lg + c) 2^slotstr.  Weights are W[K][K][in_ch][out_ch]
+ * doubles, row-major (the reference's weight[a][b][k][h]); a term is (h, k, a, b), b fastest.  The
+ * reference runs per term one host sparse encode, one EvalRotateFused, one EvalMultAutoInplace and
+ * one EvalAddAutoInplace (src/dnn.cu:99-141); here each input channel is raised once, its K^2
+ * rotations stay in the Ext basis, and one launch forms the inner sums of a pass of output channels.
+ * Refused with PHANTOM_ERR_INVALID_ARGUMENT before any launch: a null pointer, a count of 0, kernel
+ * even or larger than width, width not a power of two, ns > N/2, a chain index of 0 or past the end,
+ * no special prime, pt_scale <= 0. */
+/* the K^2 tap rotations in tap order (a, b): ((a - K/2) Lg + (b - K/2)) 2^slotstr slots, 0 for the
+ * centre tap (src/dnn.cu:114,122; AddRotationIndicesTo, :299-319).  Host only; *count = K^2 */
+int phantom_conv_rotations(size_t width, size_t slotstr, size_t kernel, int *out, size_t capacity, size_t *count);
+/* the masked slot vectors of `count` terms from first_term (src/dnn.cu:103-113, built on the host
+ * there): dev_out [count][ns] complex as interleaved (re, 0); term (h, k, a, b) holds W[a][b][k][h]
+ * at slot (r Lg + c) 2^slotstr for r, c < width with r + a - K/2 and c + b - K/2 in [0, width), 0
+ * elsewhere.  The host twin fills host memory with the same layout. */
+int phantom_conv_weight_slots(size_t width, size_t slotstr, size_t kernel, size_t in_ch, size_t out_ch,
+                              const double *dev_W, size_t first_term, size_t count, double *dev_out,
+                              hipStream_t stream);
+int phantom_conv_weight_slots_host(size_t width, size_t slotstr, size_t kernel, size_t in_ch, size_t out_ch,
+                                   const double *W, size_t first_term, size_t count, double *out);
+/* general inner sums over the Ext basis (the EvalMultExt + EvalAddExtInPlace form of
+ * src/evaluate.cu:3786-3874 for any number of terms; phantom_lt_bsgs stops at 32):
+ * outs[o] (+)= sum_{t<T} ins[t] * pts[o T + t] for o < O; ins / outs host arrays of device pointers to
+ * Ext ciphertexts, dev_pts a DEVICE table [O][T] of Ext plaintexts without null entries; accumulate
+ * != 0 adds the value already in outs[o].  The 128-bit sums are reduced every 32 terms (65 products
+ * of 61-bit residues overflow them), so the result is exact for every T. */
+int phantom_ext_mac(const phantom_context *ctx, size_t chain_index, const uint64_t *const *ins, size_t T,
+                    const uint64_t *const *dev_pts, size_t O, uint64_t *const *outs, int accumulate,
+                    hipStream_t stream);
+/* the whole layer on raw ciphertexts (src/dnn.cu:82-150): cts[k] [2][Ql][n] for k < in_ch ->
+ * outs[h] [2][Ql][n] for h < out_ch, at the input's level; the result's scale is the input's times
+ * pt_scale.  Per input channel phantom_modup of c1 and phantom_fast_rotation_ext_batch over the K^2
+ * taps (key_digits[tap]: host array of dnum device pointers, NULL at the centre tap, which takes
+ * phantom_keyswitch_ext; galois_elts[tap] its Galois element); per pass of `group` output channels
+ * (0: chosen from a byte budget for the pass's plaintexts) phantom_conv_weight_slots,
+ * phantom_ckks_encode (ext = 1, sparse_slots = ns, scale pt_scale; dev_overflow as there) and
+ * phantom_ext_mac; then phantom_moddown_from_ntt of every output polynomial, batched.  The result
+ * does not depend on group, bit for bit.  Enqueued on `stream`, scratch from the pool, not
+ * synchronised (a rotation key seen for the first time is uploaded as in phantom_keyswitch). */
+int phantom_conv2d(const phantom_context *ctx, size_t chain_index, const uint64_t *const *cts, size_t in_ch,
+                   size_t out_ch, size_t width, size_t slotstr, size_t kernel, const double *dev_W, double pt_scale,
+                   const uint64_t *const *const *key_digits, size_t dnum, const uint32_t *galois_elts, size_t group,
+                   uint64_t *const *outs, int *dev_overflow, hipStream_t stream);
+
 /* ---- serialization (host memory; no GPU involved) ------------------------------------
  * The byte format of PhantomCiphertext::save / load (include/ciphertext.h:184-225): the header
  * fields one by one (4 x size_t, double, uint64_t, size_t, bool, bool = 58 bytes) followed by

@@ -1,0 +1,131 @@
+// capi_conv.cpp — C-ABI of the hoisted encrypted convolution (declared in include/phantom_amd.h):
+// the tap rotations, the weight slot vectors and their host twin, the general inner sums over the
+// extended basis, and the whole layer on raw ciphertexts (host/conv2d.h).
+#include <vector>
+
+#include "../host/buffer.h"
+#include "../host/capi_internal.h"
+#include "../host/context.h"
+#include "../host/conv2d.h"
+#include "../host/rns_tool.h"
+#include "conv.h"
+#include "phantom_amd.h"
+
+using phantom::capi::fail;
+using phantom::capi::from_hip;
+
+const phantom::PhantomContext& phantom_capi_context(const phantom_context* c);  // capi_ckks.cpp
+const uint64_t* const* phantom_capi_key_array(const phantom_context* c, const uint64_t* const* host, size_t dnum,
+                                              size_t need);
+
+namespace {
+
+// the shape alone (no ring degree at hand): ns is checked against n = 2 ns, i.e. not at all
+phx::ConvShape shape_of(size_t width, size_t slotstr, size_t kernel, size_t in_ch, size_t out_ch) {
+  const phx::ConvShape c = phantom::conv_shape(size_t(1) << 63, width, slotstr, kernel, in_ch, out_ch);
+  return c;
+}
+
+}  // namespace
+
+extern "C" {
+
+int phantom_conv_rotations(size_t width, size_t slotstr, size_t kernel, int* out, size_t capacity, size_t* count) {
+  PHX_CAPI_GUARD({
+    if (!out || !count) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)shape_of(width, slotstr, kernel, 1, 1);
+    const std::vector<int> r = phantom::conv_rotations(width, slotstr, kernel);
+    *count = r.size();
+    if (capacity < r.size()) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "capacity below kernel^2 rotations");
+    for (size_t i = 0; i < r.size(); ++i) out[i] = r[i];
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_conv_weight_slots(size_t width, size_t slotstr, size_t kernel, size_t in_ch, size_t out_ch,
+                              const double* dev_W, size_t first_term, size_t count, double* dev_out,
+                              hipStream_t stream) {
+  PHX_CAPI_GUARD({
+    if (!dev_W || !dev_out) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    const phx::ConvShape c = shape_of(width, slotstr, kernel, in_ch, out_ch);
+    if (first_term > c.terms() || count > c.terms() - first_term)
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "terms past out_ch in_ch kernel^2");
+    return from_hip(phx::conv_weight_slots(c, dev_W, first_term, count, dev_out, stream));
+  });
+}
+
+int phantom_conv_weight_slots_host(size_t width, size_t slotstr, size_t kernel, size_t in_ch, size_t out_ch,
+                                   const double* W, size_t first_term, size_t count, double* out) {
+  PHX_CAPI_GUARD({
+    if (!W || !out) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    const phx::ConvShape c = shape_of(width, slotstr, kernel, in_ch, out_ch);
+    if (first_term > c.terms() || count > c.terms() - first_term)
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "terms past out_ch in_ch kernel^2");
+    phx::conv_weight_slots_host(c, W, first_term, count, out);
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_ext_mac(const phantom_context* ctx, size_t chain_index, const uint64_t* const* ins, size_t T,
+                    const uint64_t* const* dev_pts, size_t O, uint64_t* const* outs, int accumulate,
+                    hipStream_t stream) {
+  PHX_CAPI_GUARD({
+    const auto& pc = phantom_capi_context(ctx);
+    if (!ins || !dev_pts || !outs) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (T == 0 || O == 0 || T > (size_t(1) << 24) || O > (size_t(1) << 16))
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "term and output counts must be at least 1");
+    phx::MacArgs a = phantom::mac_args(pc, chain_index);
+    // one device table: the T input pointers, then the O output pointers
+    std::vector<uint64_t*> tab(T + O);
+    for (size_t t = 0; t < T; ++t) {
+      if (!ins[t]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null input");
+      tab[t] = const_cast<uint64_t*>(ins[t]);  // read only: the kernel takes this half as const
+    }
+    for (size_t o = 0; o < O; ++o) {
+      if (!outs[o]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null output");
+      tab[T + o] = outs[o];
+    }
+    phantom::DeviceBuffer<uint64_t*> table;
+    table.upload(tab, stream);
+    a.ins = table.get();
+    a.outs = table.get() + T;
+    a.pts = dev_pts;
+    a.T = static_cast<uint32_t>(T);
+    a.O = static_cast<uint32_t>(O);
+    a.accumulate = accumulate != 0;
+    const hipError_t e = phx::ext_mac(a, pc.poly_degree(), stream);
+    PHX_CHECK(hipStreamSynchronize(stream));  // the pointer table is freed on return
+    return from_hip(e);
+  });
+}
+
+int phantom_conv2d(const phantom_context* ctx, size_t chain_index, const uint64_t* const* cts, size_t in_ch,
+                   size_t out_ch, size_t width, size_t slotstr, size_t kernel, const double* dev_W, double pt_scale,
+                   const uint64_t* const* const* key_digits, size_t dnum, const uint32_t* galois_elts, size_t group,
+                   uint64_t* const* outs, int* dev_overflow, hipStream_t stream) {
+  PHX_CAPI_GUARD({
+    const auto& pc = phantom_capi_context(ctx);
+    if (!cts || !dev_W || !key_digits || !galois_elts || !outs) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!(pt_scale > 0)) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "scale must be positive");
+    (void)phantom::mac_args(pc, chain_index);  // the chain index and the special primes
+    const phx::ConvShape c = phantom::conv_shape(pc.poly_degree(), width, slotstr, kernel, in_ch, out_ch);
+    const size_t beta = pc.get_context_data(chain_index).gpu_rns_tool().beta();
+    const size_t K2 = kernel * kernel;
+    // every check before the first key array is uploaded (conv2d_raw repeats the rest before it enqueues)
+    for (size_t k = 0; k < in_ch; ++k)
+      if (!cts[k]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null input channel");
+    for (size_t h = 0; h < out_ch; ++h)
+      if (!outs[h]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null output channel");
+    for (size_t t = 0; t < K2; ++t)
+      if (!key_digits[t] && t != K2 / 2)
+        return fail(PHANTOM_ERR_INVALID_ARGUMENT, "only the centre tap goes without a rotation key");
+    std::vector<const uint64_t* const*> evk(K2, nullptr);
+    for (size_t t = 0; t < K2; ++t)
+      if (key_digits[t]) evk[t] = phantom_capi_key_array(ctx, key_digits[t], dnum, beta);
+    phantom::conv2d_raw(pc, chain_index, cts, c, dev_W, pt_scale, evk.data(), galois_elts, group, outs, dev_overflow,
+                        stream);
+    return PHANTOM_OK;
+  });
+}
+
+}  // extern "C"

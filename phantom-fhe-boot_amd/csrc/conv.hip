@@ -1,0 +1,317 @@
+// conv.hip — kernels of the hoisted encrypted convolution (see conv.h).
+#include "conv.h"
+
+#include <algorithm>
+
+#include "arith.h"
+
+namespace phx {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr uint64_t kM30 = (1ull << 30) - 1;
+
+// operand k of a list given as a device pointer table or as base + k stride
+__device__ __forceinline__ const uint64_t* mac_in(const MacArgs& a, uint32_t t) {
+  return a.ins ? a.ins[t] : a.in0 + static_cast<size_t>(t) * a.in_stride;
+}
+__device__ __forceinline__ const uint64_t* mac_pt(const MacArgs& a, size_t k) {
+  return a.pts ? a.pts[k] : a.pt0 + k * a.pt_stride;
+}
+__device__ __forceinline__ uint64_t* mac_out(const MacArgs& a, uint32_t o) {
+  return a.outs ? a.outs[o] : a.out0 + static_cast<size_t>(o) * a.out_stride;
+}
+
+// 16-byte global (not flat) accesses of two consecutive elements: they count in vmcnt only
+typedef uint64_t mac_u64x2 __attribute__((ext_vector_type(2)));
+struct MacVec {
+  uint64_t v[kMacEpl];
+};
+__device__ __forceinline__ MacVec mac_ld(const uint64_t* p) {
+  const mac_u64x2 x = *(const __attribute__((address_space(1))) mac_u64x2*)p;
+  MacVec r;
+  r.v[0] = x.x;
+  r.v[1] = x.y;
+  return r;
+}
+
+// the four 64-bit partial sums of x * w per element and polynomial, x and w split in 30-bit halves
+struct MacPart {
+  uint64_t ll, m1, m2, hh;
+};
+
+__device__ __forceinline__ void mac_fold(u128& acc, MacPart& P) {
+  add128(acc, u128{P.ll, 0});
+  add128(acc, u128{P.m1 << 30, P.m1 >> 34});
+  add128(acc, u128{P.m2 << 30, P.m2 >> 34});
+  add128(acc, u128{P.hh << 60, P.hh >> 4});
+  P = MacPart{0, 0, 0, 0};
+}
+
+constexpr int kMacChunk = 4, kMacChunks = kMacBlock / kMacChunk;
+
+// chunk c (terms 4c .. 4c + 3 of the block at t0) of output o's plaintexts; terms past the last
+// read the last one again (their inputs are staged as zeros)
+__device__ __forceinline__ void mac_load_chunk(MacVec (&w)[kMacChunk], const MacArgs& a, size_t prow, uint32_t t0, int c,
+                                               size_t e) {
+#pragma unroll
+  for (int j = 0; j < kMacChunk; ++j) {
+    const uint32_t t = min(t0 + static_cast<uint32_t>(c * kMacChunk + j), a.T - 1);
+    w[j] = mac_ld(mac_pt(a, prow + t) + e);
+  }
+}
+
+// part += sum_j in(4c + j) * w[j], the inputs from LDS (row 2j + p: term j of the block,
+// polynomial p, as {low 30, high 30} bits)
+__device__ __forceinline__ void mac_chunk_products(MacPart (&part)[kMacEpl][2], const MacVec (&w)[kMacChunk],
+                                                   const uint2 (*xs)[kMacTile], int c, int lane) {
+#pragma unroll
+  for (int jj = 0; jj < kMacChunk; ++jj) {
+    const int j = c * kMacChunk + jj;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const uint4 xx = *reinterpret_cast<const uint4*>(&xs[2 * j + p][2 * lane]);
+      const uint2 x[kMacEpl] = {make_uint2(xx.x, xx.y), make_uint2(xx.z, xx.w)};
+#pragma unroll
+      for (int k = 0; k < kMacEpl; ++k) {
+        const uint32_t wl = static_cast<uint32_t>(w[jj].v[k] & kM30), wh = static_cast<uint32_t>(w[jj].v[k] >> 30);
+        MacPart& P = part[k][p];
+        P.ll += static_cast<uint64_t>(x[k].x) * wl;
+        P.m1 += static_cast<uint64_t>(x[k].x) * wh;
+        P.m2 += static_cast<uint64_t>(x[k].y) * wl;
+        P.hh += static_cast<uint64_t>(x[k].y) * wh;
+      }
+    }
+  }
+}
+
+// One workgroup = kMacWaves waves over one tile of kMacTile elements; grid row y serves outputs
+// 8 y .. 8 y + 7, wave w output 8 y + w.  Per block of kMacBlock terms: every wave loads 8 of the 64
+// input rows (32 terms x 2 polynomials; rows past the last term are zeros) and writes them to LDS
+// as 30-bit halves; then each wave with an output streams that output's 32 plaintexts 4 at a time,
+// chunk c + 1's loads in flight while chunk c's products run.  The 128-bit sums stay in registers
+// and are reduced below q after every block (conv.h).
+template <bool Q60>
+__global__ __launch_bounds__(64 * kMacWaves) void ext_mac_tile_kernel(MacArgs a, uint32_t log_n, size_t total) {
+  constexpr int E = kMacEpl;
+  __shared__ uint2 xs[2 * kMacBlock][kMacTile];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const size_t tile = blockIdx.x;
+  const size_t e = tile * kMacTile + static_cast<size_t>(lane) * E;
+  const uint32_t o = blockIdx.y * kMacWaves + wv;
+  const bool active = o < a.O;  // wave-uniform
+  const int l = static_cast<int>((tile * kMacTile) >> log_n);
+  const int row = l < static_cast<int>(a.Ql) ? l : static_cast<int>(a.size_Q) + (l - static_cast<int>(a.Ql));
+  const uint64_t q = a.q[row], r0 = a.barrett[2 * row], r1 = a.barrett[2 * row + 1];
+  const size_t prow = static_cast<size_t>(active ? o : 0) * a.T;
+  uint64_t* const op = active ? mac_out(a, o) : nullptr;
+
+  u128 acc[E][2];
+  MacPart part[E][2];
+#pragma unroll
+  for (int k = 0; k < E; ++k)
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      acc[k][p] = u128{0, 0};
+      part[k][p] = MacPart{0, 0, 0, 0};
+    }
+  if (active && a.accumulate) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const MacVec old = mac_ld(op + p * total + e);
+#pragma unroll
+      for (int k = 0; k < E; ++k) acc[k][p].lo = old.v[k];
+    }
+  }
+
+  for (uint32_t t0 = 0; t0 < a.T; t0 += kMacBlock) {
+    const int nb = static_cast<int>(min(a.T - t0, static_cast<uint32_t>(kMacBlock)));
+    // staging: wave wv loads rows wv + 8 r, r < 8 (row 2 j + p: term t0 + j, polynomial p)
+    MacVec v[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int R = wv + 8 * r, j = R >> 1;
+      if (j < nb) v[r] = mac_ld(mac_in(a, t0 + j) + static_cast<size_t>(R & 1) * total + e);
+      else v[r] = MacVec{{0, 0}};
+    }
+    MacVec wbuf[2][kMacChunk];
+    if (active) mac_load_chunk(wbuf[0], a, prow, t0, 0, e);
+    if (t0) __syncthreads();  // the previous block's LDS reads are done
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+      for (int k = 0; k < E; ++k)
+        xs[wv + 8 * r][lane * E + k] =
+            make_uint2(static_cast<uint32_t>(v[r].v[k] & kM30), static_cast<uint32_t>(v[r].v[k] >> 30));
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int c = 0; c < kMacChunks; ++c) {
+        if (c * kMacChunk >= nb) break;  // the rest of a tail block is zeros
+        if (c + 1 < kMacChunks) mac_load_chunk(wbuf[(c + 1) & 1], a, prow, t0, c + 1, e);
+        // keep the next chunk's loads together and ahead of this chunk's products
+        __builtin_amdgcn_sched_barrier(0);
+        mac_chunk_products(part, wbuf[c & 1], xs, c, lane);
+        // 8 products per partial sum (q < 2^60: each below 2^60, the sum below 2^63), otherwise 4
+        // (a high-half product reaches 2^62)
+        if ((c & 1) || !Q60) {
+#pragma unroll
+          for (int k = 0; k < E; ++k)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) mac_fold(acc[k][p], part[k][p]);
+        }
+      }
+      // a tail block may stop between folds; then the block's sum (at most 32 products and the
+      // carried residue, below 2^128) is reduced and carried on
+#pragma unroll
+      for (int k = 0; k < E; ++k)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          mac_fold(acc[k][p], part[k][p]);
+          acc[k][p] = u128{barrett_reduce_128(acc[k][p], q, r0, r1), 0};
+        }
+    }
+  }
+  if (active) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      mac_u64x2 r;
+      r.x = acc[0][p].lo;
+      r.y = acc[1][p].lo;
+      *(__attribute__((address_space(1))) mac_u64x2*)(op + p * total + e) = r;
+    }
+  }
+}
+
+// One element per thread and grid-stride step, grid row y = output y: any n and any tile
+// alignment.  Terms 4 at a time (4 products per partial sum fit for every modulus below 2^61),
+// the 128-bit sum reduced below q every kMacBlock terms.
+__global__ __launch_bounds__(kBlock) void ext_mac_plain_kernel(MacArgs a, uint32_t log_n, size_t total) {
+  const uint32_t o = blockIdx.y;
+  uint64_t* const op = mac_out(a, o);
+  const size_t prow = static_cast<size_t>(o) * a.T;
+  for (size_t e = blockIdx.x * (size_t)kBlock + threadIdx.x; e < total; e += (size_t)gridDim.x * kBlock) {
+    const int l = static_cast<int>(e >> log_n);
+    const int row = l < static_cast<int>(a.Ql) ? l : static_cast<int>(a.size_Q) + (l - static_cast<int>(a.Ql));
+    const uint64_t q = a.q[row], r0 = a.barrett[2 * row], r1 = a.barrett[2 * row + 1];
+    u128 acc[2] = {{0, 0}, {0, 0}};
+    if (a.accumulate) {
+      acc[0].lo = op[e];
+      acc[1].lo = op[total + e];
+    }
+    for (uint32_t t0 = 0; t0 < a.T; t0 += kMacChunk) {
+      const uint32_t cnt = min(a.T - t0, static_cast<uint32_t>(kMacChunk));
+      MacPart part[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+      for (uint32_t j = 0; j < cnt; ++j) {
+        const uint64_t* in = mac_in(a, t0 + j);
+        const uint64_t w = mac_pt(a, prow + t0 + j)[e];
+        const uint32_t wl = static_cast<uint32_t>(w & kM30), wh = static_cast<uint32_t>(w >> 30);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const uint64_t x = in[p * total + e];
+          const uint32_t xl = static_cast<uint32_t>(x & kM30), xh = static_cast<uint32_t>(x >> 30);
+          part[p].ll += static_cast<uint64_t>(xl) * wl;
+          part[p].m1 += static_cast<uint64_t>(xl) * wh;
+          part[p].m2 += static_cast<uint64_t>(xh) * wl;
+          part[p].hh += static_cast<uint64_t>(xh) * wh;
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        mac_fold(acc[p], part[p]);
+        if ((t0 + kMacChunk) % kMacBlock == 0) acc[p] = u128{barrett_reduce_128(acc[p], q, r0, r1), 0};
+      }
+    }
+    op[e] = barrett_reduce_128(acc[0], q, r0, r1);
+    op[total + e] = barrett_reduce_128(acc[1], q, r0, r1);
+  }
+}
+
+// thread i: slot i % ns of term first + i / ns
+__global__ __launch_bounds__(kBlock) void conv_weight_slots_kernel(ConvShape c, const double* W, size_t first, size_t total,
+                                                                   uint32_t log_ns, double2* out) {
+  const uint32_t K = c.kernel, half = K / 2, lg = c.width << c.slotstr;
+  const uint32_t log_lg = log_ns / 2;
+  for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kBlock) {
+    const uint32_t s = static_cast<uint32_t>(i & ((size_t(1) << log_ns) - 1));
+    size_t term = first + (i >> log_ns);
+    const uint32_t b = term % K;
+    term /= K;
+    const uint32_t ta = term % K;
+    term /= K;
+    const uint32_t k = term % c.in_ch, h = static_cast<uint32_t>(term / c.in_ch);
+    double v = 0.0;
+    if ((s & ((1u << c.slotstr) - 1)) == 0) {
+      const uint32_t m = s >> c.slotstr, r = m >> log_lg, col = m & (lg - 1);
+      // r + a - K/2 and col + b - K/2 in [0, width)
+      if (r < c.width && col < c.width && r + ta >= half && r + ta < half + c.width && col + b >= half &&
+          col + b < half + c.width)
+        v = W[((static_cast<size_t>(ta) * K + b) * c.in_ch + k) * c.out_ch + h];
+    }
+    out[i] = make_double2(v, 0.0);
+  }
+}
+
+__global__ __launch_bounds__(64) void write_words_kernel(uint64_t* dst, Words w, uint32_t count) {
+  for (uint32_t i = threadIdx.x; i < count; i += 64) dst[i] = w.w[i];
+}
+
+unsigned grid_for(size_t total) { return static_cast<unsigned>(std::min<size_t>((total + kBlock - 1) / kBlock, 65535)); }
+
+}  // namespace
+
+hipError_t ext_mac(const MacArgs& a, size_t n, hipStream_t s) {
+  if (a.T == 0 || a.O == 0 || n == 0 || (n & (n - 1))) return hipErrorInvalidValue;
+  if ((!a.ins && !a.in0) || (!a.pts && !a.pt0) || (!a.outs && !a.out0)) return hipErrorInvalidValue;
+  const size_t total = static_cast<size_t>(a.Ql + a.P) * n;
+  const uint32_t log_n = static_cast<uint32_t>(__builtin_ctzll(n));
+  if (n >= kMacTileMinN && n % kMacTile == 0) {
+    // a tile never crosses a limb (n is a multiple of it)
+    const dim3 grid(static_cast<unsigned>(total / kMacTile), (a.O + kMacWaves - 1) / kMacWaves);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    if (a.q60) ext_mac_tile_kernel<true><<<grid, 64 * kMacWaves, 0, s>>>(a, log_n, total);
+    else ext_mac_tile_kernel<false><<<grid, 64 * kMacWaves, 0, s>>>(a, log_n, total);
+  } else {
+    if (a.O > 65535) return hipErrorInvalidValue;
+    ext_mac_plain_kernel<<<dim3(grid_for(total), a.O), kBlock, 0, s>>>(a, log_n, total);
+  }
+  return hipGetLastError();
+}
+
+hipError_t conv_weight_slots(const ConvShape& c, const double* dev_W, size_t first_term, size_t count, double* dev_out,
+                             hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  const size_t ns = c.slots(), total = count * ns;
+  conv_weight_slots_kernel<<<grid_for(total), kBlock, 0, s>>>(c, dev_W, first_term, total,
+                                                             static_cast<uint32_t>(__builtin_ctzll(ns)),
+                                                             reinterpret_cast<double2*>(dev_out));
+  return hipGetLastError();
+}
+
+void conv_weight_slots_host(const ConvShape& c, const double* W, size_t first_term, size_t count, double* out) {
+  const size_t K = c.kernel, half = K / 2, lg = c.large(), ns = c.slots(), pw = size_t(1) << c.slotstr;
+  std::fill(out, out + 2 * count * ns, 0.0);
+  for (size_t i = 0; i < count; ++i) {
+    size_t term = first_term + i;
+    const size_t b = term % K;
+    term /= K;
+    const size_t a = term % K;
+    term /= K;
+    const size_t k = term % c.in_ch, h = term / c.in_ch;
+    const double w = W[((a * K + b) * c.in_ch + k) * c.out_ch + h];
+    for (size_t r = 0; r < c.width; ++r)
+      for (size_t col = 0; col < c.width; ++col)
+        if (r + a >= half && r + a < half + c.width && col + b >= half && col + b < half + c.width)
+          out[2 * (i * ns + (r * lg + col) * pw)] = w;
+  }
+}
+
+hipError_t write_words(uint64_t* dst, const Words& w, size_t count, hipStream_t s) {
+  if (count > static_cast<size_t>(kWordsMax)) return hipErrorInvalidValue;
+  if (count == 0) return hipSuccess;
+  write_words_kernel<<<1, 64, 0, s>>>(dst, w, static_cast<uint32_t>(count));
+  return hipGetLastError();
+}
+
+}  // namespace phx

@@ -1,0 +1,167 @@
+// conv2d.cpp — see conv2d.h
+#include "conv2d.h"
+
+#include <algorithm>
+#include <complex>
+#include <cstring>
+#include <stdexcept>
+
+#include "../csrc/rns.h"
+#include "buffer.h"
+#include "encoder.h"
+#include "hip_check.h"
+#include "rns_tool.h"
+
+namespace phantom {
+
+phx::ConvShape conv_shape(size_t n, size_t width, size_t slotstr, size_t kernel, size_t in_ch, size_t out_ch) {
+  if (width == 0 || (width & (width - 1))) throw std::invalid_argument("conv: width must be a power of two");
+  if (kernel % 2 == 0 || kernel > width) throw std::invalid_argument("conv: kernel must be odd and at most width");
+  if (in_ch == 0 || out_ch == 0) throw std::invalid_argument("conv: no channels");
+  if (in_ch > (size_t(1) << 20) || out_ch > (size_t(1) << 20)) throw std::invalid_argument("conv: too many channels");
+  // ns = (width 2^slotstr)^2 <= n / 2, checked without overflow
+  if (slotstr >= 32 || (width << slotstr) > (size_t(1) << 31)) throw std::invalid_argument("conv: slot stride too large");
+  const size_t lg = width << slotstr;
+  if (lg * lg > n / 2) throw std::invalid_argument("conv: the image does not fit the slots");
+  phx::ConvShape c;
+  c.width = static_cast<uint32_t>(width);
+  c.slotstr = static_cast<uint32_t>(slotstr);
+  c.kernel = static_cast<uint32_t>(kernel);
+  c.in_ch = static_cast<uint32_t>(in_ch);
+  c.out_ch = static_cast<uint32_t>(out_ch);
+  return c;
+}
+
+std::vector<int> conv_rotations(size_t width, size_t slotstr, size_t kernel) {
+  const long lg = static_cast<long>(width << slotstr), half = static_cast<long>(kernel / 2);
+  std::vector<int> r;
+  r.reserve(kernel * kernel);
+  for (long a = 0; a < static_cast<long>(kernel); ++a)
+    for (long b = 0; b < static_cast<long>(kernel); ++b)
+      r.push_back(static_cast<int>(((a - half) * lg + (b - half)) * (1l << slotstr)));
+  return r;
+}
+
+size_t conv_group(const PhantomContext& ctx, size_t chain_index, const phx::ConvShape& c) {
+  const size_t QlP = ctx.get_context_data(chain_index).gpu_rns_tool().size_Ql() + ctx.size_P();
+  const size_t per_output = static_cast<size_t>(c.in_ch) * c.kernel * c.kernel * QlP * ctx.poly_degree() * sizeof(uint64_t);
+  return std::clamp<size_t>(kConvPlainBudget / per_output, 1, c.out_ch);
+}
+
+phx::MacArgs mac_args(const PhantomContext& ctx, size_t chain_index) {
+  if (chain_index < 1 || chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  if (ctx.size_P() == 0) throw std::invalid_argument("no special primes");
+  phx::MacArgs a;
+  a.Ql = static_cast<uint32_t>(ctx.get_context_data(chain_index).gpu_rns_tool().size_Ql());
+  a.P = static_cast<uint32_t>(ctx.size_P());
+  a.size_Q = static_cast<uint32_t>(ctx.size_Q());
+  a.q = ctx.mod_QP().q;
+  a.barrett = ctx.mod_QP().barrett;
+  a.q60 = below_2_60(ctx.key_moduli());
+  return a;
+}
+
+void conv2d_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, const phx::ConvShape& c,
+                const double* dev_W, double pt_scale, const uint64_t* const* const* evk, const uint32_t* galois_elts,
+                size_t group, uint64_t* const* outs, int* dev_overflow, hipStream_t s) {
+  if (!cts || !dev_W || !evk || !galois_elts || !outs) throw std::invalid_argument("null pointer");
+  if (!(pt_scale > 0)) throw std::invalid_argument("scale must be positive");
+  phx::MacArgs ma = mac_args(ctx, chain_index);  // checks the chain index and the special primes
+  const size_t n = ctx.poly_degree();
+  (void)conv_shape(n, c.width, c.slotstr, c.kernel, c.in_ch, c.out_ch);
+  const RnsTool& rt = ctx.get_context_data(chain_index).gpu_rns_tool();
+  const size_t Ql = rt.size_Ql(), QlP = Ql + ctx.size_P(), beta = rt.beta();
+  const size_t K2 = static_cast<size_t>(c.kernel) * c.kernel, T = c.in_ch * K2, ns = c.slots();
+  const size_t centre = K2 / 2;
+  for (size_t k = 0; k < c.in_ch; ++k)
+    if (!cts[k]) throw std::invalid_argument("null input channel");
+  for (size_t h = 0; h < c.out_ch; ++h)
+    if (!outs[h]) throw std::invalid_argument("null output channel");
+  for (size_t t = 0; t < K2; ++t)
+    if (!evk[t] && t != centre) throw std::invalid_argument("conv: only the centre tap goes without a rotation key");
+  if (group == 0) group = conv_group(ctx, chain_index, c);
+  group = std::min<size_t>(group, c.out_ch);
+  const size_t ext_words = 2 * QlP * n, pt_words = QlP * n, ct_words = 2 * Ql * n;
+  const phx::NttTables& ntt = ctx.gpu_rns_tables();
+
+  // the K^2 rotations' entries, the same for every input channel (outputs tap ext_words apart)
+  std::vector<phx::KsBatchEntry> e(K2);
+  for (size_t t = 0; t < K2; ++t) {
+    if (evk[t]) {
+      e[t].evk = evk[t];
+      e[t].perm = ctx.galois_perm(galois_elts[t]);
+      e[t].binv = ctx.galois_block_inv(galois_elts[t]);
+    }
+    e[t].out_off = static_cast<int64_t>(t * ext_words);
+  }
+  static_assert(sizeof(phx::KsBatchEntry) % sizeof(uint64_t) == 0, "entries are copied as words");
+  const size_t entry_words = K2 * sizeof(phx::KsBatchEntry) / sizeof(uint64_t);
+  DeviceBuffer<uint64_t> table(entry_words, s);
+  for (size_t w0 = 0; w0 < entry_words; w0 += phx::kWordsMax) {
+    const size_t cnt = std::min<size_t>(phx::kWordsMax, entry_words - w0);
+    phx::Words w;
+    std::memcpy(w.w, reinterpret_cast<const uint64_t*>(e.data()) + w0, cnt * sizeof(uint64_t));
+    hip_ok(phx::write_words(table.get() + w0, w, cnt, s), "conv rotation table");
+  }
+
+  // every rotation of every input channel in the extended basis: term (k, tap) at rots + (k K^2 + tap) ext_words
+  DeviceBuffer<uint64_t> rots(T * ext_words, s), digits(beta * QlP * n, s);
+  phx::KsRotateBatchArgs ba;
+  ba.digits = digits.get();
+  ba.entries = reinterpret_cast<const phx::KsBatchEntry*>(table.get());
+  ba.count = static_cast<uint32_t>(K2);
+  ba.qp = ctx.mod_QP().q;
+  ba.qp_barrett = ctx.mod_QP().barrett;
+  ba.pmod = rt.bigP_mod_q();
+  ba.pmod_shoup = rt.bigP_mod_q_shoup();
+  ba.ql = static_cast<uint32_t>(Ql);
+  ba.qlp = static_cast<uint32_t>(QlP);
+  ba.size_q = static_cast<uint32_t>(ctx.size_Q());
+  ba.size_p = static_cast<uint32_t>(ctx.size_P());
+  ba.beta = static_cast<uint32_t>(beta);
+  for (size_t k = 0; k < c.in_ch; ++k) {
+    rt.modup(digits.get(), cts[k] + Ql * n, ntt, s);
+    ba.ct = cts[k];
+    ba.out = rots.get() + k * K2 * ext_words;
+    hip_ok(phx::keyswitch_rotate_batch(ba, n, s), "conv rotations");
+  }
+
+  // inner sums, `group` output channels per pass
+  DeviceBuffer<uint64_t> acc(c.out_ch * ext_words, s), pts(group * T * pt_words, s);
+  DeviceBuffer<double> slots(group * T * ns * 2, s);
+  ma.in0 = rots.get();
+  ma.in_stride = ext_words;
+  ma.pt0 = pts.get();
+  ma.pt_stride = pt_words;
+  ma.out_stride = ext_words;
+  ma.T = static_cast<uint32_t>(T);
+  for (size_t h0 = 0; h0 < c.out_ch; h0 += group) {
+    const size_t g = std::min(group, c.out_ch - h0);
+    hip_ok(phx::conv_weight_slots(c, dev_W, h0 * T, g * T, slots.get(), s), "conv weight slots");
+    encode_raw(ctx, chain_index, true, reinterpret_cast<const std::complex<double>*>(slots.get()), ns, ns, pt_scale,
+               g * T, pts.get(), nullptr, dev_overflow, s);
+    ma.out0 = acc.get() + h0 * ext_words;
+    ma.O = static_cast<uint32_t>(g);
+    hip_ok(phx::ext_mac(ma, n, s), "conv inner sums");
+  }
+
+  // moddown of the 2 out_ch output polynomials, 8 per launch set (the fused conversion's batch)
+  const bool contiguous = [&] {
+    for (size_t h = 1; h < c.out_ch; ++h)
+      if (outs[h] != outs[0] + h * ct_words) return false;
+    return true;
+  }();
+  DeviceBuffer<uint64_t> stage;
+  if (!contiguous) stage.allocate(c.out_ch * ct_words, s);
+  uint64_t* const dst = contiguous ? outs[0] : stage.get();
+  constexpr size_t kPer = 4;  // output channels per moddown
+  for (size_t h0 = 0; h0 < c.out_ch; h0 += kPer) {
+    const size_t g = std::min(kPer, c.out_ch - h0);
+    rt.moddown_add(dst + h0 * ct_words, acc.get() + h0 * ext_words, false, ntt, s, 2 * g);
+  }
+  if (!contiguous)
+    for (size_t h = 0; h < c.out_ch; ++h)
+      PHX_CHECK(hipMemcpyAsync(outs[h], stage.get() + h * ct_words, ct_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+}
+
+}  // namespace phantom

@@ -1,0 +1,194 @@
+// dnn.cpp — see dnn.h
+#include "dnn.h"
+
+#include <cmath>
+#include <complex>
+#include <stdexcept>
+#include <unordered_set>
+
+#include "buffer.h"
+#include "conv2d.h"
+#include "hip_check.h"
+
+namespace phantom {
+
+using cplx = std::complex<double>;
+
+void DNN::RelinKeyGen(PhantomSecretKey& secret_key) { mul_key_ = secret_key.gen_relinkey(context_); }
+
+void DNN::BuildGaloisKey(PhantomSecretKey& secret_key, std::vector<int32_t>& rotation_indices) {
+  gk_ = secret_key.EvalRotateKeyGen(context_, rotation_indices);
+}
+
+void DNN::AddRotationIndicesTo(std::vector<int32_t>& rotation_indices, size_t input_width, size_t kernel_h,
+                               size_t slotstr) {
+  std::unordered_set<int32_t> existing(rotation_indices.begin(), rotation_indices.end());
+  for (int r : conv_rotations(input_width, slotstr, kernel_h))
+    if (existing.insert(r).second) rotation_indices.push_back(r);
+}
+
+void DNN::ComputeRotationIndices(PhantomSecretKey& secret_key, size_t input_width, size_t kernel_h, size_t slotstr) {
+  std::vector<int32_t> idx;
+  AddRotationIndicesTo(idx, input_width, kernel_h, slotstr);
+  BuildGaloisKey(secret_key, idx);
+}
+
+PhantomPlaintext DNN::PlainTextEncode(const std::vector<double>& input, size_t chain_index) {
+  PhantomPlaintext x_plain;
+  encoder_.encode_sparse(context_, input, static_cast<double>(scale_), x_plain, chain_index);
+  return x_plain;
+}
+
+TensorCT DNN::EncTensor(const Tensor3& input, PhantomPublicKey& pk, size_t slotstr) {
+  if (input.empty() || input[0].size() != input.size() || input[0][0].empty())
+    throw std::invalid_argument("EncTensor: input must be [width][width][channels]");
+  TensorCT result;
+  result.width_ = input.size();
+  result.num_ch_ = input[0][0].size();
+  result.slotstr_ = slotstr;
+  const size_t width = result.width_, ch = result.num_ch_;
+  const phx::ConvShape shape = conv_shape(context_.poly_degree(), width, slotstr, 1, ch, 1);
+  const size_t lg = shape.large(), ns = shape.slots(), pw = size_t(1) << slotstr;
+  std::vector<cplx> values(ch * ns, cplx(0.0, 0.0));
+  for (size_t i = 0; i < width; ++i) {
+    if (input[i].size() != width) throw std::invalid_argument("EncTensor: input must be [width][width][channels]");
+    for (size_t j = 0; j < width; ++j) {
+      if (input[i][j].size() != ch) throw std::invalid_argument("EncTensor: ragged channels");
+      for (size_t k = 0; k < ch; ++k) values[k * ns + (i * lg + j) * pw] = input[i][j][k];
+    }
+  }
+  DeviceBuffer<cplx> dv;
+  dv.upload(values, context_.stream());
+  encoder_.set_sparse_encode(2 * ns);
+  result.ctks_.resize(ch);
+  pk.encrypt_asymmetric_sparse_batch(context_, encoder_, dv.get(), ns, static_cast<double>(scale_), 1, result.ctks_);
+  return result;
+}
+
+DNN::Tensor3 DNN::DecTensor(const TensorCT& t, PhantomSecretKey& sk) {
+  const size_t width = t.width_, ch = t.num_ch_;
+  if (ch == 0 || t.ctks_.size() != ch) throw std::invalid_argument("DecTensor: channel count mismatch");
+  const phx::ConvShape shape = conv_shape(context_.poly_degree(), width, t.slotstr_, 1, ch, 1);
+  const size_t lg = shape.large(), pw = size_t(1) << t.slotstr_, slots = encoder_.slot_count();
+  DeviceBuffer<cplx> dv(ch * slots, context_.stream());
+  sk.decrypt_decode_batch(context_, encoder_, t.ctks_, 0, dv.get());
+  // sparse packing repeats the (width 2^slotstr)^2 values in every block: the first block is read
+  const std::vector<cplx> v = dv.download(context_.stream());
+  Tensor3 out(width, std::vector<std::vector<double>>(width, std::vector<double>(ch)));
+  for (size_t k = 0; k < ch; ++k)
+    for (size_t i = 0; i < width; ++i)
+      for (size_t j = 0; j < width; ++j) out[i][j][k] = v[k * slots + (i * lg + j) * pw].real();
+  return out;
+}
+
+TensorCT DNN::Conv(const TensorCT& input, const Weight4& weight, size_t stride) {
+  if (weight.empty() || weight[0].size() != weight.size() || weight[0][0].empty() || weight[0][0][0].empty())
+    throw std::invalid_argument("Conv: weight must be [K][K][in_ch][out_ch]");
+  const size_t K = weight.size(), in_ch = weight[0][0].size(), out_ch = weight[0][0][0].size();
+  std::vector<double> w(K * K * in_ch * out_ch);
+  for (size_t a = 0; a < K; ++a) {
+    if (weight[a].size() != K) throw std::invalid_argument("Conv: weight must be [K][K][in_ch][out_ch]");
+    for (size_t b = 0; b < K; ++b) {
+      if (weight[a][b].size() != in_ch) throw std::invalid_argument("Conv: ragged weight");
+      for (size_t k = 0; k < in_ch; ++k) {
+        if (weight[a][b][k].size() != out_ch) throw std::invalid_argument("Conv: ragged weight");
+        for (size_t h = 0; h < out_ch; ++h) w[((a * K + b) * in_ch + k) * out_ch + h] = weight[a][b][k][h];
+      }
+    }
+  }
+  if (in_ch != input.num_ch_) throw std::invalid_argument("Conv: the weight's input channels differ from the tensor's");
+  DeviceBuffer<double> dW;
+  dW.upload(w, context_.stream());
+  return Conv(input, dW.get(), K, out_ch, stride);
+}
+
+TensorCT DNN::Conv(const TensorCT& input, const double* dev_W, size_t kernel_h, size_t out_ch, size_t stride) {
+  if (stride != 1 && stride != 2) throw std::invalid_argument("Conv: stride must be 1 or 2");
+  const size_t in_ch = input.num_ch_, n = context_.poly_degree();
+  if (in_ch == 0 || input.ctks_.size() != in_ch) throw std::invalid_argument("Conv: channel count mismatch");
+  if (!dev_W) throw std::invalid_argument("Conv: null weights");
+  const PhantomCiphertext& first = input.ctks_[0];
+  for (const PhantomCiphertext& c : input.ctks_)
+    if (c.size() != 2 || c.chain_index() != first.chain_index() || c.scale() != first.scale() ||
+        c.GetNoiseScaleDeg() != first.GetNoiseScaleDeg())
+      throw std::invalid_argument("Conv: the channels must share level, noise-scale degree and scale");
+  const phx::ConvShape shape = conv_shape(n, input.width_, input.slotstr_, kernel_h, in_ch, out_ch);
+  // a degree-2 input is rescaled first (EvalMultAutoInplace, src/evaluate.cu:2813-2825)
+  std::vector<PhantomCiphertext> rescaled;
+  if (first.GetNoiseScaleDeg() == 2) {
+    rescaled = input.ctks_;
+    for (PhantomCiphertext& c : rescaled) EvalModReduceInPlace(context_, c, 1);
+  }
+  const std::vector<PhantomCiphertext>& in = rescaled.empty() ? input.ctks_ : rescaled;
+  const size_t chain = in[0].chain_index();
+
+  const std::vector<int> rots = conv_rotations(input.width_, input.slotstr_, kernel_h);
+  std::vector<const uint64_t* const*> evk(rots.size(), nullptr);
+  std::vector<uint32_t> elts(rots.size(), 1);
+  for (size_t t = 0; t < rots.size(); ++t) {
+    if (rots[t] == 0) continue;  // the centre tap
+    elts[t] = FindAutomorphismIndex2nComplex(rots[t], n);
+    if (!gk_.has(elts[t])) throw std::invalid_argument("Conv: no rotation key for a tap (ComputeRotationIndices)");
+    evk[t] = gk_.get(elts[t]).public_keys_ptr();
+  }
+
+  TensorCT result;
+  result.width_ = input.width_ / stride;
+  result.num_ch_ = out_ch;
+  result.slotstr_ = stride == 2 ? input.slotstr_ + 1 : input.slotstr_;
+  result.ctks_.resize(out_ch);
+  hipStream_t s = context_.stream();
+  std::vector<const uint64_t*> cts(in_ch);
+  std::vector<uint64_t*> outs(out_ch);
+  for (size_t k = 0; k < in_ch; ++k) cts[k] = in[k].data();
+  for (size_t h = 0; h < out_ch; ++h) {
+    PhantomCiphertext& o = result.ctks_[h];
+    o.resize(context_, chain, 2, s, false);
+    o.set_ntt_form(true);
+    o.set_scale(in[0].scale() * static_cast<double>(scale_));
+    o.SetNoiseScaleDeg(in[0].GetNoiseScaleDeg() + 1);
+    o.set_correction_factor(in[0].correction_factor());
+    o.set_asymmetric(in[0].is_asymmetric());
+    outs[h] = o.data();
+  }
+  encoder_.set_sparse_encode(2 * shape.slots());
+  conv2d_raw(context_, chain, cts.data(), shape, dev_W, static_cast<double>(scale_), evk.data(), elts.data(), 0,
+             outs.data(), nullptr, s);
+  return result;
+}
+
+TensorCT DNN::BatchNorm(const TensorCT& input, const std::vector<double>& weight, const std::vector<double>& bias,
+                        const std::vector<double>& mean, const std::vector<double>& var) {
+  const size_t ch = input.num_ch_;
+  if (input.ctks_.size() != ch || weight.size() != ch || bias.size() != ch || mean.size() != ch || var.size() != ch)
+    throw std::invalid_argument("BatchNorm: one weight, bias, mean and variance per channel");
+  const double eps = 1e-5;
+  TensorCT output;
+  output.ctks_.resize(ch);
+  output.width_ = input.width_;
+  output.num_ch_ = ch;
+  output.slotstr_ = input.slotstr_;
+  for (size_t c = 0; c < ch; ++c) {
+    const double a = weight[c] / std::sqrt(var[c] + eps);
+    const double b = bias[c] - a * mean[c];
+    output.ctks_[c] = EvalMultConst(context_, input.ctks_[c], a, m_scalingFactorsReal_);
+    EvalAddConstInPlaceWrap(context_, output.ctks_[c], b, m_scalingFactorsReal_, m_scalingFactorsRealBig_);
+  }
+  return output;
+}
+
+TensorCT DNN::Add(const TensorCT& a, const TensorCT& b) {
+  if (a.num_ch_ != b.num_ch_ || a.width_ != b.width_ || a.slotstr_ != b.slotstr_ || a.ctks_.size() != a.num_ch_ ||
+      b.ctks_.size() != b.num_ch_)
+    throw std::invalid_argument("TensorCT dimension mismatch in Add()");
+  TensorCT result;
+  result.num_ch_ = a.num_ch_;
+  result.width_ = a.width_;
+  result.slotstr_ = a.slotstr_;
+  result.ctks_.resize(a.num_ch_);
+  for (size_t u = 0; u < a.num_ch_; ++u)
+    result.ctks_[u] = EvalAddAuto(context_, a.ctks_[u], b.ctks_[u], m_scalingFactorsReal_, m_scalingFactorsRealBig_);
+  return result;
+}
+
+}  // namespace phantom

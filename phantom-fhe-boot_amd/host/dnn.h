@@ -1,0 +1,90 @@
+// dnn.h — the reference's privacy-preserving ML layer façade (include/dnn.cuh, src/dnn.cu) on this
+// engine: TensorCT and the DNN members that encrypt a tensor, convolve it, and chain two
+// convolutions (BatchNorm, Add).  Conv is the hoisted layer of host/conv2d.h instead of the
+// reference's out_ch in_ch K^2 rotate / multiply / add steps (src/dnn.cu:82-150); EncTensor and
+// DecTensor are one batched device call each.
+//
+// Not built here: Relu, ReluDegTwo, Sign, ReluComposite, SoftMax, AvgPoolFullCon,
+// BootStrap, the weight loader and the ResNet driver.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "ciphertext.h"
+#include "ckks_eval.h"
+#include "context.h"
+#include "encoder.h"
+#include "keys.h"
+
+namespace phantom {
+
+// one ciphertext per channel: a width_ x width_ image in (width_ 2^slotstr_)^2 sparse-packed slots,
+// pixel (r, c) at slot (r width_ 2^slotstr_ + c) 2^slotstr_ (include/dnn.cuh:33-39)
+struct TensorCT {
+  std::vector<PhantomCiphertext> ctks_;
+  size_t width_ = 0;
+  size_t slotstr_ = 0;
+  size_t num_ch_ = 0;
+};
+
+class DNN {
+ public:
+  using Tensor3 = std::vector<std::vector<std::vector<double>>>;  // [width][width][channel]
+  using Weight4 = std::vector<std::vector<std::vector<std::vector<double>>>>;  // [K][K][in_ch][out_ch]
+
+  DNN(size_t scale, PhantomCKKSEncoder& encoder, const PhantomContext& context)
+      : scale_(scale), context_(context), encoder_(encoder) {}
+
+  void setScalingFactors(const std::vector<double>& scalingFactorsReal, const std::vector<double>& scalingFactorsRealBig) {
+    m_scalingFactorsReal_ = scalingFactorsReal;
+    m_scalingFactorsRealBig_ = scalingFactorsRealBig;
+  }
+  void RelinKeyGen(PhantomSecretKey& secret_key);
+  // fused rotation keys (EvalRotateKeyGen) for the given slot rotations
+  void BuildGaloisKey(PhantomSecretKey& secret_key, std::vector<int32_t>& rotation_indices);
+  // ... for the K^2 taps of one layer geometry (src/dnn.cu:270-297)
+  void ComputeRotationIndices(PhantomSecretKey& secret_key, size_t input_width, size_t kernel_h, size_t slotstr);
+  // appends the taps' rotations that the list lacks (src/dnn.cu:299-319)
+  void AddRotationIndicesTo(std::vector<int32_t>& rotation_indices, size_t input_width, size_t kernel_h, size_t slotstr);
+  // what a caller needs to run its own steps beside the layers (examples/conv_example.cpp's baseline)
+  const PhantomGaloisKeyFused& galois_keys() const { return gk_; }
+  const std::vector<double>& scalingFactorsReal() const { return m_scalingFactorsReal_; }
+  const std::vector<double>& scalingFactorsRealBig() const { return m_scalingFactorsRealBig_; }
+
+  // encode_sparse at scale_ (src/dnn.cu:75-80); the encoder's sparse slot count is the caller's
+  PhantomPlaintext PlainTextEncode(const std::vector<double>& input, size_t chain_index);
+  // input[i][j][k] -> one ciphertext per channel at chain index 1 (src/dnn.cu:10-40): the slot
+  // vectors are built channel-major, uploaded once and encrypted by one batched public-key call with
+  // sparse_slots = (width 2^slotstr)^2 (the encoder is left set to that packing).  slotstr > 0
+  // packs the pixels 2^slotstr slots apart, the layout a stride-2 layer leaves.
+  TensorCT EncTensor(const Tensor3& input, PhantomPublicKey& pk, size_t slotstr = 0);
+  // one batched decrypt + decode (src/dnn.cu:42-71)
+  Tensor3 DecTensor(const TensorCT& enc_tensor, PhantomSecretKey& sk);
+
+  // weight[a][b][k][h] (src/dnn.cu:82-150).  stride 1 or 2: stride 2 halves width_ and raises
+  // slotstr_ by one, nothing else (:145-147).  The result is at the input's level with noise-scale
+  // degree input + 1 and scale ct.scale * scale_; a degree-2 input is rescaled first, as
+  // EvalMultAutoInplace does.  std::invalid_argument: mismatched channel counts, channels at
+  // different levels, degrees or scales, a stride other than 1 or 2, a missing rotation key.
+  TensorCT Conv(const TensorCT& input, const Weight4& weight, size_t stride);
+  // the same with the weights already on the device: dev_W [K][K][in_ch][out_ch] doubles, complete
+  // in the context's stream order
+  TensorCT Conv(const TensorCT& input, const double* dev_W, size_t kernel_h, size_t out_ch, size_t stride);
+  // per channel a x + b with a = weight / sqrt(var + 1e-5), b = bias - a mean (src/dnn.cu:454-480)
+  TensorCT BatchNorm(const TensorCT& input, const std::vector<double>& weight, const std::vector<double>& bias,
+                     const std::vector<double>& mean, const std::vector<double>& var);
+  // channel-wise EvalAddAuto (src/dnn.cu:482-501)
+  TensorCT Add(const TensorCT& a, const TensorCT& b);
+
+ private:
+  size_t scale_;
+  PhantomGaloisKeyFused gk_;
+  const PhantomContext& context_;
+  PhantomCKKSEncoder& encoder_;
+  std::vector<double> m_scalingFactorsReal_;
+  std::vector<double> m_scalingFactorsRealBig_;
+  PhantomRelinKey mul_key_;
+};
+
+}  // namespace phantom

@@ -135,6 +135,13 @@ _SIGS = {
     "phantom_encrypt_asymmetric_batch_chunk": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
     "phantom_boot_encrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp, sz, ctypes.POINTER(sz)]),
     "phantom_boot_decrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp]),
+    "phantom_conv_rotations": (ctypes.c_int, [sz, sz, sz, vp, sz, ctypes.POINTER(sz)]),
+    "phantom_conv_weight_slots": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp, vp]),
+    "phantom_conv_weight_slots_host": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp]),
+    "phantom_ext_mac": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, vp, sz, ctypes.POINTER(vp), ctypes.c_int, vp]),
+    "phantom_conv2d": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, sz, sz, sz, sz, vp, ctypes.c_double,
+                                      ctypes.POINTER(ctypes.POINTER(vp)), sz, ctypes.POINTER(ctypes.c_uint32), sz,
+                                      ctypes.POINTER(vp), vp, vp]),
 }
 
 _lib = None
@@ -444,6 +451,41 @@ class LtPrep:
     @staticmethod
     def dense_diagonals(dev_A, slots, scale, dev_out, dev_flags, stream):
         check(load().phantom_ltprep_dense_diagonals(dev_A, slots, scale, dev_out, dev_flags, stream))
+
+
+class Conv:
+    """The hoisted encrypted convolution's helpers (phantom_conv_*).  A shape is (width, slotstr,
+    kernel, in_ch, out_ch); weights are float64 [K, K, in_ch, out_ch]; slot vectors are complex128
+    [count, ns] with ns = (width 2^slotstr)^2, terms ordered (h, k, a, b) with b fastest."""
+
+    @staticmethod
+    def slots(width, slotstr):
+        return (width << slotstr) ** 2
+
+    @staticmethod
+    def rotations(width, slotstr, kernel):
+        import numpy as np
+        out = np.zeros(kernel * kernel, dtype=np.int32)
+        cnt = sz(0)
+        check(load().phantom_conv_rotations(width, slotstr, kernel, out.ctypes.data, out.size, ctypes.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    @staticmethod
+    def weight_slots_host(shape, W, first_term, count):
+        import numpy as np
+        width, slotstr, kernel, in_ch, out_ch = shape
+        w = np.ascontiguousarray(W, dtype=np.float64)
+        assert w.shape == (kernel, kernel, in_ch, out_ch)
+        out = np.zeros((count, Conv.slots(width, slotstr)), dtype=np.complex128)
+        check(load().phantom_conv_weight_slots_host(width, slotstr, kernel, in_ch, out_ch, w.ctypes.data, first_term,
+                                                    count, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def weight_slots(shape, dev_W, first_term, count, dev_out, stream):
+        width, slotstr, kernel, in_ch, out_ch = shape
+        check(load().phantom_conv_weight_slots(width, slotstr, kernel, in_ch, out_ch, dev_W, first_term, count,
+                                               dev_out, stream))
 
 
 def ptr_array(ptrs):
