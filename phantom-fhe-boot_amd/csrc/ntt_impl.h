@@ -1222,11 +1222,13 @@ void ntt_row(KArgs a) {
   }
 }
 // ---------------------------------------------------------------------------------------
-// 1-D path for small transforms, n = 2^8 .. 2^11 (the reference's radix-2 fnwt_1d / inwt_1d,
-// src/ntt/ntt_1d.cu): one workgroup of n/2 threads per limb, the limb in LDS, one butterfly per
-// thread and stage, the reference's in-place loop order and twiddle indices (tw[m + j]).  Integer
-// Shoup butterflies for every prime; the prologue / epilogue / scale of the 2-D path are honoured
-// so every launcher works at these degrees.
+// 1-D path for small transforms, n = 2^3 .. 2^11 (the reference's radix-2 fnwt_1d / inwt_1d,
+// src/ntt/ntt_1d.cu): one workgroup of max(64, n/2) threads per limb, the limb in LDS, one butterfly
+// per thread and stage, the reference's in-place loop order and twiddle indices (tw[m + j]).  Only
+// the first n/2 threads run butterflies: there j < m, so m + j < 2m <= n stays inside the limb's
+// table row (below n = 128 the rest of the wavefront would index past it).  Integer Shoup
+// butterflies for every prime; the prologue / epilogue / scale of the 2-D path are honoured so
+// every launcher works at these degrees.
 // ---------------------------------------------------------------------------------------
 constexpr int kMaxLog1D = 11;
 
@@ -1253,20 +1255,24 @@ __global__ __launch_bounds__(1024) void ntt_1d(KArgs a) {
   __syncthreads();
   if constexpr (FWD) {
     for (int m = 1, t = half; m < n; m <<= 1, t >>= 1) {
-      const int j = i / t, k = i % t, i1 = 2 * j * t + k;
-      uint64_t x = v[i1], y = v[i1 + t];
-      ct_bfly(x, y, tw[m + j], tws[m + j], q);
-      v[i1] = x;
-      v[i1 + t] = y;
+      if (i < (uint32_t)half) {  // the block is at least one wavefront: idle threads would read tw past n
+        const int j = i / t, k = i % t, i1 = 2 * j * t + k;
+        uint64_t x = v[i1], y = v[i1 + t];
+        ct_bfly(x, y, tw[m + j], tws[m + j], q);
+        v[i1] = x;
+        v[i1 + t] = y;
+      }
       __syncthreads();
     }
   } else {
     for (int m = half, t = 1; m >= 1; m >>= 1, t <<= 1) {
-      const int j = i / t, k = i % t, i1 = 2 * j * t + k;
-      uint64_t x = v[i1], y = v[i1 + t];
-      gs_bfly(x, y, tw[m + j], tws[m + j], q);
-      v[i1] = x;
-      v[i1 + t] = y;
+      if (i < (uint32_t)half) {
+        const int j = i / t, k = i % t, i1 = 2 * j * t + k;
+        uint64_t x = v[i1], y = v[i1 + t];
+        gs_bfly(x, y, tw[m + j], tws[m + j], q);
+        v[i1] = x;
+        v[i1 + t] = y;
+      }
       __syncthreads();
     }
   }

@@ -5,8 +5,8 @@ radix-2 embedding for the FP64 stage, and a float64 numpy restatement of the hos
 radix-2 algorithm (PhantomCKKSEncoder::fft) for the error the project accepts today.
 
 Shapes: N = 2^12 and 2^13 with CoeffModulus::Create(N, [60, 40, 40, 60]) (one special prime: chains
-of 3, 2 and 1 data limbs) and one N = 2^16 case.  The embedding and the split kernels take the same
-two-pass plan at every N, so there is no switch to straddle.
+of 3, 2 and 1 data limbs); the embedding and the whole encode / decode chain at every N from 2^10
+to 2^17 (EMBED_LOG_N: the embedding's single-tile branch up to N = 2048, even and odd splits above).
 """
 import random
 
@@ -125,7 +125,12 @@ def embed_forward(R, c, sparse_slots=0, count=1):
 
 # ---- FP stage: the embedding -------------------------------------------------------------------
 
-@pytest.mark.parametrize("log_n", [12, 13, 16])
+# csrc/encode.hip splits log_n into s1 = (log_n + 1) / 2 and s2: 10 is below its single-tile bound
+# (kTile = 2048), 11 equals it, 14 / 15 are an even and an odd split, 17 the largest degree
+EMBED_LOG_N = [10, 11, 12, 13, 14, 15, 16, 17]
+
+
+@pytest.mark.parametrize("log_n", EMBED_LOG_N)
 def test_embed_inverse_error_against_longdouble(rng, log_n):
     R = ring(log_n)
     v = unit_square(rng, R.n // 2)
@@ -137,7 +142,7 @@ def test_embed_inverse_error_against_longdouble(rng, log_n):
     assert e_dev <= 4 * e_host
 
 
-@pytest.mark.parametrize("log_n", [12, 13, 16])
+@pytest.mark.parametrize("log_n", EMBED_LOG_N)
 def test_embed_forward_error_against_longdouble(rng, log_n):
     R = ring(log_n)
     c = rng.uniform(-1, 1, R.n)
@@ -148,7 +153,7 @@ def test_embed_forward_error_against_longdouble(rng, log_n):
     assert e_dev <= 4 * e_host
 
 
-@pytest.mark.parametrize("log_n", [12, 13])
+@pytest.mark.parametrize("log_n", [10, 11, 12, 13, 15])
 def test_embed_sparse_agrees_with_dense_tiling(rng, log_n):
     R = ring(log_n)
     ns = R.n // 8
@@ -297,7 +302,7 @@ def test_compose_centred_integers(chain):
 
 # ---- whole chain -------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("log_n", [12, 13, 16])
+@pytest.mark.parametrize("log_n", EMBED_LOG_N)
 def test_decode_of_encode_returns_the_input(rng, log_n):
     """max error of decode(encode(v)) at scale 2^40 against 4 x the error of the host algorithm
     (float64 radix-2 embedding, exact rounding and exact integers) on the same v"""

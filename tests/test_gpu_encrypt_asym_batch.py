@@ -141,7 +141,7 @@ def values_in(rng, shape, lo=-1.0, hi=1.0):
 
 
 @pytest.mark.parametrize("chain", [1, 2, 3])
-@pytest.mark.parametrize("log_n", [12, 13])
+@pytest.mark.parametrize("log_n", [10, 12, 13, 15])
 def test_encrypt_equals_the_sequential_entries(rng, log_n, chain):
     R = ring(log_n)
     n, slots = R.n, R.n // 2
