@@ -333,6 +333,33 @@ int phantom_conv2d(const phantom_context *ctx, size_t chain_index, const uint64_
                    size_t out_ch, size_t width, size_t slotstr, size_t kernel, const double *dev_W, double pt_scale,
                    const uint64_t *const *const *key_digits, size_t dnum, const uint32_t *galois_elts, size_t group,
                    uint64_t *const *outs, int *dev_overflow, hipStream_t stream);
+/* phantom_ext_mac over compact plaintexts (phantom_ckks_encode_sub): dev_pts[k] is [Ql + P][sub_degree]
+ * and word e of a limb multiplies plaintext word e >> log2(N / sub_degree):
+ *   outs[o][p][l][e] (+)= sum_{t<T} ins[t][p][l][e] * pts[o T + t][l][e >> log2(N / sub_degree)]  mod q_l.
+ * The arithmetic is phantom_ext_mac's, exact for every T; sub_degree is a power of two in [1, N], and
+ * sub_degree = N is phantom_ext_mac itself (full-size plaintexts, the same kernel). */
+int phantom_ext_mac_sub(const phantom_context *ctx, size_t chain_index, const uint64_t *const *ins, size_t T,
+                        const uint64_t *const *dev_pts, size_t sub_degree, size_t O, uint64_t *const *outs,
+                        int accumulate, hipStream_t stream);
+/* A prepared layer (the weights of src/dnn.cu:82-150 are fixed across inferences; the reference
+ * encodes them per call with its sparse encoder, src/ckks.cu:180-270).  prepare runs
+ * phantom_conv_weight_slots -> phantom_ckks_encode_sub (ext = 1, sub_slots = ns, scale pt_scale) for
+ * all out_ch in_ch K^2 terms into one device allocation owned by the plan (8 out_ch in_ch K^2
+ * (Ql + P) 2 ns bytes, phantom_conv_plan_bytes), waits for `stream`, and never reads dev_W again.
+ * apply is phantom_conv2d with the plan in place of the weights: the modups and batched rotations,
+ * ONE phantom_ext_mac_sub over all output channels, the batched moddown; enqueued in order, no
+ * synchronisation, no encode.  Refused (status 1, outputs untouched): every shape phantom_conv2d
+ * refuses, 2 ns < 8, a context other than the plan's, a null key at a tap other than the centre, a
+ * null pointer.  phantom_conv_plan_destroy frees the plan; no apply may be in flight. */
+typedef struct phantom_conv_plan phantom_conv_plan;
+int phantom_conv2d_prepare(const phantom_context *ctx, size_t chain_index, size_t in_ch, size_t out_ch, size_t width,
+                           size_t slotstr, size_t kernel, const double *dev_W, double pt_scale, int *dev_overflow,
+                           hipStream_t stream, phantom_conv_plan **plan);
+int phantom_conv_plan_bytes(const phantom_conv_plan *plan, size_t *bytes);
+int phantom_conv_plan_destroy(phantom_conv_plan *plan);
+int phantom_conv2d_apply(const phantom_context *ctx, const phantom_conv_plan *plan, const uint64_t *const *cts,
+                         const uint64_t *const *const *key_digits, size_t dnum, const uint32_t *galois_elts,
+                         uint64_t *const *outs, hipStream_t stream);
 
 /* ---- serialization (host memory; no GPU involved) ------------------------------------
  * The byte format of PhantomCiphertext::save / load (include/ciphertext.h:184-225): the header
@@ -412,6 +439,21 @@ int phantom_ckks_compose(const phantom_context *ctx, size_t chain_index, const u
 int phantom_ckks_encode(const phantom_context *ctx, size_t chain_index, int ext, const double *values,
                         size_t num_values, size_t sparse_slots, double scale, size_t count, uint64_t *out,
                         int *dev_overflow, hipStream_t stream);
+/* The compact sparse encoder (the reference's sparse path, src/ckks.cu:180-270: a size-ns FFT,
+ * decompose_array over 2 ns coefficients, extend_sparse_ckks).  With M = 2 sub_slots and g = N / M, a
+ * plaintext p(X) = p'(X^g) has NTT_N(p)[i] = NTT'_M(p')[i >> log2 g] in the engine's bit-reversed
+ * order, NTT'_M the size-M negacyclic transform with root psi_N^g (its twiddles are the first M
+ * entries of the size-N table), so p' alone is kept: values [count][num_values] complex (num_values
+ * <= sub_slots, zero-padded) -> out [count][limbs][M], the size-M inverse embedding, the round and
+ * split over M coefficients and NTT'_M.  sub_slots = N/2 gives phantom_ckks_encode bit for bit.
+ * phantom_sub_ntt is NTT'_M (inverse != 0: its exact inverse, M^-1 included) in place on data
+ * [count][limbs][sub_degree].  Refused (status 1, nothing enqueued): a subring degree that is not a
+ * power of two in [8, N], a bad chain index, a null pointer, scale <= 0. */
+int phantom_ckks_encode_sub(const phantom_context *ctx, size_t chain_index, int ext, const double *values,
+                            size_t num_values, size_t sub_slots, double scale, size_t count, uint64_t *out,
+                            int *dev_overflow, hipStream_t stream);
+int phantom_sub_ntt(const phantom_context *ctx, size_t chain_index, int ext, size_t sub_degree, int inverse,
+                    uint64_t *data, size_t count, hipStream_t stream);
 /* PhantomCKKSEncoder::decode_internal (src/ckks.cu:456-521): plain [count][Ql][N] (NTT form, not
  * modified) -> values [count][N/2] complex = embedding(centred coefficients / scale) */
 int phantom_ckks_decode(const phantom_context *ctx, size_t chain_index, const uint64_t *plain, double scale,

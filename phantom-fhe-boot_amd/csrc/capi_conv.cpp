@@ -1,6 +1,7 @@
 // capi_conv.cpp — C-ABI of the hoisted encrypted convolution (declared in include/phantom_amd.h):
 // the tap rotations, the weight slot vectors and their host twin, the general inner sums over the
 // extended basis, and the whole layer on raw ciphertexts (host/conv2d.h).
+#include <memory>
 #include <vector>
 
 #include "../host/buffer.h"
@@ -17,6 +18,11 @@ using phantom::capi::from_hip;
 const phantom::PhantomContext& phantom_capi_context(const phantom_context* c);  // capi_ckks.cpp
 const uint64_t* const* phantom_capi_key_array(const phantom_context* c, const uint64_t* const* host, size_t dnum,
                                               size_t need);
+
+struct phantom_conv_plan {
+  std::unique_ptr<phantom::ConvPlanData> data;
+  const phantom_context* owner = nullptr;
+};
 
 namespace {
 
@@ -124,6 +130,101 @@ int phantom_conv2d(const phantom_context* ctx, size_t chain_index, const uint64_
       if (key_digits[t]) evk[t] = phantom_capi_key_array(ctx, key_digits[t], dnum, beta);
     phantom::conv2d_raw(pc, chain_index, cts, c, dev_W, pt_scale, evk.data(), galois_elts, group, outs, dev_overflow,
                         stream);
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_ext_mac_sub(const phantom_context* ctx, size_t chain_index, const uint64_t* const* ins, size_t T,
+                        const uint64_t* const* dev_pts, size_t sub_degree, size_t O, uint64_t* const* outs,
+                        int accumulate, hipStream_t stream) {
+  PHX_CAPI_GUARD({
+    const auto& pc = phantom_capi_context(ctx);
+    if (!ins || !dev_pts || !outs) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (T == 0 || O == 0 || T > (size_t(1) << 24) || O > (size_t(1) << 16))
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "term and output counts must be at least 1");
+    if (sub_degree == 0 || sub_degree > pc.poly_degree() || (sub_degree & (sub_degree - 1)))
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "the subring degree must be a power of two in [1, N]");
+    phx::MacArgs a = phantom::mac_args(pc, chain_index);
+    // one device table: the T input pointers, then the O output pointers
+    std::vector<uint64_t*> tab(T + O);
+    for (size_t t = 0; t < T; ++t) {
+      if (!ins[t]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null input");
+      tab[t] = const_cast<uint64_t*>(ins[t]);  // read only: the kernel takes this half as const
+    }
+    for (size_t o = 0; o < O; ++o) {
+      if (!outs[o]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null output");
+      tab[T + o] = outs[o];
+    }
+    phantom::DeviceBuffer<uint64_t*> table;
+    table.upload(tab, stream);
+    a.ins = table.get();
+    a.outs = table.get() + T;
+    a.pts = dev_pts;
+    a.T = static_cast<uint32_t>(T);
+    a.O = static_cast<uint32_t>(O);
+    a.accumulate = accumulate != 0;
+    const hipError_t e = phx::ext_mac_sub(a, pc.poly_degree(), sub_degree, stream);
+    PHX_CHECK(hipStreamSynchronize(stream));  // the pointer table is freed on return
+    return from_hip(e);
+  });
+}
+
+int phantom_conv2d_prepare(const phantom_context* ctx, size_t chain_index, size_t in_ch, size_t out_ch, size_t width,
+                           size_t slotstr, size_t kernel, const double* dev_W, double pt_scale, int* dev_overflow,
+                           hipStream_t stream, phantom_conv_plan** plan) {
+  PHX_CAPI_GUARD({
+    const auto& pc = phantom_capi_context(ctx);
+    if (!dev_W || !plan) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!(pt_scale > 0)) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "scale must be positive");
+    (void)phantom::mac_args(pc, chain_index);
+    const phx::ConvShape c = phantom::conv_shape(pc.poly_degree(), width, slotstr, kernel, in_ch, out_ch);
+    auto p = std::make_unique<phantom_conv_plan>();
+    p->data = phantom::conv2d_prepare(pc, chain_index, c, dev_W, pt_scale, dev_overflow, stream);
+    p->owner = ctx;
+    *plan = p.release();
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_conv_plan_bytes(const phantom_conv_plan* plan, size_t* bytes) {
+  PHX_CAPI_GUARD({
+    if (!plan || !bytes) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    *bytes = plan->data->bytes();
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_conv_plan_destroy(phantom_conv_plan* plan) {
+  PHX_CAPI_GUARD({
+    delete plan;
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_conv2d_apply(const phantom_context* ctx, const phantom_conv_plan* plan, const uint64_t* const* cts,
+                         const uint64_t* const* const* key_digits, size_t dnum, const uint32_t* galois_elts,
+                         uint64_t* const* outs, hipStream_t stream) {
+  PHX_CAPI_GUARD({
+    const auto& pc = phantom_capi_context(ctx);
+    if (!plan || !cts || !key_digits || !galois_elts || !outs)
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (plan->owner != ctx || plan->data->ctx != &pc)
+      return fail(PHANTOM_ERR_INVALID_ARGUMENT, "the plan was prepared for another context");
+    const phx::ConvShape& c = plan->data->shape;
+    const size_t beta = pc.get_context_data(plan->data->chain_index).gpu_rns_tool().beta();
+    const size_t K2 = static_cast<size_t>(c.kernel) * c.kernel;
+    // every check before the first key array is uploaded (conv2d_apply repeats them before it enqueues)
+    for (size_t k = 0; k < c.in_ch; ++k)
+      if (!cts[k]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null input channel");
+    for (size_t h = 0; h < c.out_ch; ++h)
+      if (!outs[h]) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null output channel");
+    for (size_t t = 0; t < K2; ++t)
+      if (!key_digits[t] && t != K2 / 2)
+        return fail(PHANTOM_ERR_INVALID_ARGUMENT, "only the centre tap goes without a rotation key");
+    std::vector<const uint64_t* const*> evk(K2, nullptr);
+    for (size_t t = 0; t < K2; ++t)
+      if (key_digits[t]) evk[t] = phantom_capi_key_array(ctx, key_digits[t], dnum, beta);
+    phantom::conv2d_apply(pc, *plan->data, cts, evk.data(), galois_elts, outs, stream);
     return PHANTOM_OK;
   });
 }

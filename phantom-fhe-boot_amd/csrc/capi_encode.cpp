@@ -48,6 +48,26 @@ int phantom_ckks_encode(const phantom_context* ctx, size_t chain_index, int ext,
   });
 }
 
+int phantom_ckks_encode_sub(const phantom_context* ctx, size_t chain_index, int ext, const double* values,
+                            size_t num_values, size_t sub_slots, double scale, size_t count, uint64_t* out,
+                            int* dev_overflow, hipStream_t stream) {
+  PHX_CAPI_GUARD({
+    phantom::encode_sub_raw(phantom_capi_context(ctx), chain_index, ext != 0,
+                            reinterpret_cast<const std::complex<double>*>(values), num_values, sub_slots, scale, count,
+                            out, dev_overflow, stream);
+    return PHANTOM_OK;
+  });
+}
+
+int phantom_sub_ntt(const phantom_context* ctx, size_t chain_index, int ext, size_t sub_degree, int inverse,
+                    uint64_t* data, size_t count, hipStream_t stream) {
+  PHX_CAPI_GUARD({
+    phantom::sub_ntt_raw(phantom_capi_context(ctx), chain_index, ext != 0, sub_degree, inverse != 0, data, count,
+                         stream);
+    return PHANTOM_OK;
+  });
+}
+
 int phantom_ckks_decode(const phantom_context* ctx, size_t chain_index, const uint64_t* plain, double scale,
                         size_t count, double* values, hipStream_t stream) {
   PHX_CAPI_GUARD({

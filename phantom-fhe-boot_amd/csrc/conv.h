@@ -51,6 +51,24 @@ struct MacArgs {
 };
 hipError_t ext_mac(const MacArgs& a, size_t n, hipStream_t s);
 
+// ---- the same sums over compact plaintexts ---------------------------------------------------
+//   out[o][p][l][e] (+)= sum_{t < T} in[t][p][l][e] * pt[o T + t][l][e >> log2(n / sub_degree)]   (mod q_l)
+// pt[k]: [Ql + P][sub_degree], the subring form of a sparse-packed plaintext (host/encoder.h
+// encode_sub_raw: a polynomial in X^(n / sub_degree) takes equal NTT values on blocks of
+// g = n / sub_degree words); sub_degree is a power of two in [1, n].  The arithmetic contract is
+// ext_mac's (30-bit halves, folds every 8 / 4 products, Barrett reduction every kMacBlock terms), so
+// the result is exact for any T and equals ext_mac on the plaintexts expanded g-fold.
+//
+// Plaintext traffic is 1/g of the input traffic, so the kernel is bound by the input bytes and the
+// multiplies, and the tile is chosen for those: one workgroup = kSubWaves = 16 waves over one
+// 128-element tile, each wave one output, the staged block of 32 inputs x 2 polynomials (64 KiB of
+// LDS) shared by 16 outputs (ext_mac: 8).  1,024 threads and 64 KiB leave one workgroup of 4 waves
+// per SIMD on a CU, at most 128 VGPRs per lane; the sums, the double-buffered plaintext words and the
+// prefetched rows fit without scratch.  Other shapes (n < kMacTileMinN) take a
+// one-element-per-thread form.
+constexpr int kSubWaves = 16;
+hipError_t ext_mac_sub(const MacArgs& a, size_t n, size_t sub_degree, hipStream_t s);
+
 // ---- the weight tensor as masked slot vectors ------------------------------------------------
 // W: [K][K][in_ch][out_ch] doubles, row-major (the reference's weight[a][b][k][h]).  With
 // pow = 2^slotstr, Lg = width pow and ns = Lg^2, term (h, k, a, b) is a real vector of ns slots,

@@ -228,6 +228,216 @@ __global__ __launch_bounds__(kBlock) void ext_mac_plain_kernel(MacArgs a, uint32
   }
 }
 
+// ---- inner sums over compact plaintexts (conv.h) ---------------------------------------------
+// chunk c of output o's plaintext words, one per lane (shared by the lane's two elements); byte
+// offset `pofs` from each plaintext's base, 32 bits so that the load takes the scalar base and a
+// vector offset
+__device__ __forceinline__ void sub_load_chunk(uint64_t (&w)[kMacChunk], const MacArgs& a, size_t prow, uint32_t t0,
+                                               int c, uint32_t pofs) {
+#pragma unroll
+  for (int j = 0; j < kMacChunk; ++j) {
+    const uint32_t t = min(t0 + static_cast<uint32_t>(c * kMacChunk + j), a.T - 1);
+    w[j] = *(const __attribute__((address_space(1))) uint64_t*)(reinterpret_cast<const char*>(mac_pt(a, prow + t)) + pofs);
+  }
+}
+
+// as mac_chunk_products with one word per lane; Uniform: the word is the same in every lane and
+// its halves go to scalar registers once per term
+template <bool Uniform>
+__device__ __forceinline__ void sub_chunk_products(MacPart (&part)[kMacEpl][2], const uint64_t (&w)[kMacChunk],
+                                                   const uint2 (*xs)[kMacTile], int c, int lane) {
+#pragma unroll
+  for (int jj = 0; jj < kMacChunk; ++jj) {
+    const int j = c * kMacChunk + jj;
+    uint32_t wl = static_cast<uint32_t>(w[jj] & kM30), wh = static_cast<uint32_t>(w[jj] >> 30);
+    if constexpr (Uniform) {
+      wl = __builtin_amdgcn_readfirstlane(wl);
+      wh = __builtin_amdgcn_readfirstlane(wh);
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const uint4 xx = *reinterpret_cast<const uint4*>(&xs[2 * j + p][2 * lane]);
+      const uint2 x[kMacEpl] = {make_uint2(xx.x, xx.y), make_uint2(xx.z, xx.w)};
+#pragma unroll
+      for (int k = 0; k < kMacEpl; ++k) {
+        MacPart& P = part[k][p];
+        P.ll += static_cast<uint64_t>(x[k].x) * wl;
+        P.m1 += static_cast<uint64_t>(x[k].x) * wh;
+        P.m2 += static_cast<uint64_t>(x[k].y) * wl;
+        P.hh += static_cast<uint64_t>(x[k].y) * wh;
+      }
+    }
+  }
+}
+
+// One workgroup = kSubWaves = 16 waves over one tile of kMacTile elements, wave w forming output
+// 16 row + w: a staged block of 32 inputs x 2 polynomials serves 16 outputs, so a layer of up to 16
+// output channels reads every input once.  Wave w stages rows w + 16 r, r < 4; the rows of the next
+// block are loaded one per two chunks while this block's products run (behind the next chunk's
+// plaintext words, so the wait for those words leaves the row in flight), and written to LDS after
+// the barrier that ends the block.  Plaintext words (gap >= 2; gap 1 is ext_mac): one per lane,
+// shared by its two elements, or with Uniform (gap >= 128) one per tile, its halves in scalar
+// registers.  Every address is a wave-uniform base and a 32-bit lane offset, which leaves the
+// address registers to the sums.  Workgroups are numbered so
+// that the rows of one tile follow each other on one XCD (blocks b and b + 8 share one): with more
+// than 16 outputs the re-read of a tile's inputs can hit that XCD's L2.  Placement is for speed
+// only; nothing depends on it.
+constexpr int kSubRows = 2 * kMacBlock / kSubWaves;
+// 16 bytes at base + ofs (a scalar base and a vector offset)
+__device__ __forceinline__ MacVec sub_ld2(const uint64_t* base, uint32_t ofs) {
+  return mac_ld(reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(base) + ofs));
+}
+template <bool Q60, bool Uniform>
+__global__ __launch_bounds__(64 * kSubWaves) void ext_mac_sub_tile_kernel(MacArgs a, uint32_t log_n, uint32_t log_g,
+                                                                          uint32_t rows, size_t total) {
+  constexpr int E = kMacEpl;
+  __shared__ uint2 xs[2 * kMacBlock][kMacTile];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t b = blockIdx.x, bi = b >> 3;
+  const size_t tile = static_cast<size_t>(bi / rows) * 8 + (b & 7);
+  const size_t e0 = tile * kMacTile;  // the tile's first element (wave-uniform)
+  const uint32_t lofs = static_cast<uint32_t>(lane) * (E * sizeof(uint64_t));  // the lane's bytes into the tile
+  const uint32_t o = (bi % rows) * kSubWaves + wv;
+  const bool active = o < a.O;  // wave-uniform
+  const int l = static_cast<int>((tile * kMacTile) >> log_n);
+  const int row = l < static_cast<int>(a.Ql) ? l : static_cast<int>(a.size_Q) + (l - static_cast<int>(a.Ql));
+  const uint64_t q = a.q[row], r0 = a.barrett[2 * row], r1 = a.barrett[2 * row + 1];
+  const size_t prow = static_cast<size_t>(active ? o : 0) * a.T;
+  uint64_t* const op = active ? mac_out(a, o) : nullptr;
+  // the lane's plaintext word in limb l of [Ql + P][n >> log_g], as a byte offset (a plaintext has
+  // at most 64 limbs of 2^17 words)
+  const uint32_t ein = static_cast<uint32_t>(e0 & ((size_t(1) << log_n) - 1)) + static_cast<uint32_t>(lane) * E;
+  const uint32_t pofs = ((static_cast<uint32_t>(l) << (log_n - log_g)) + (ein >> log_g)) * sizeof(uint64_t);
+
+  u128 acc[E][2];
+  MacPart part[E][2];
+#pragma unroll
+  for (int k = 0; k < E; ++k)
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      acc[k][p] = u128{0, 0};
+      part[k][p] = MacPart{0, 0, 0, 0};
+    }
+  if (active && a.accumulate) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const MacVec old = sub_ld2(op + p * total + e0, lofs);
+#pragma unroll
+      for (int k = 0; k < E; ++k) acc[k][p].lo = old.v[k];
+    }
+  }
+
+  // row R = wv + 16 r of the block at t0: term t0 + R / 2, polynomial R % 2; zeros past the last term
+  auto load_row = [&](uint32_t t0, int r) -> MacVec {
+    const int R = wv + kSubWaves * r;
+    const uint32_t t = t0 + static_cast<uint32_t>(R >> 1);
+    if (t < a.T) return sub_ld2(mac_in(a, t) + static_cast<size_t>(R & 1) * total + e0, lofs);
+    return MacVec{{0, 0}};
+  };
+  MacVec v[kSubRows];
+#pragma unroll
+  for (int r = 0; r < kSubRows; ++r) v[r] = load_row(0, r);
+
+  for (uint32_t t0 = 0; t0 < a.T; t0 += kMacBlock) {
+    const int nb = static_cast<int>(min(a.T - t0, static_cast<uint32_t>(kMacBlock)));
+    const bool more = t0 + kMacBlock < a.T;  // then nb = kMacBlock and every chunk below runs
+    uint64_t wbuf[2][kMacChunk];
+    if (active) sub_load_chunk(wbuf[0], a, prow, t0, 0, pofs);
+    if (t0) __syncthreads();  // the previous block's LDS reads are done
+#pragma unroll
+    for (int r = 0; r < kSubRows; ++r)
+#pragma unroll
+      for (int k = 0; k < E; ++k)
+        xs[wv + kSubWaves * r][lane * E + k] =
+            make_uint2(static_cast<uint32_t>(v[r].v[k] & kM30), static_cast<uint32_t>(v[r].v[k] >> 30));
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < kMacChunks; ++c) {
+      if (c * kMacChunk >= nb) break;  // the rest of a tail block is zeros
+      if (active && c + 1 < kMacChunks) sub_load_chunk(wbuf[(c + 1) & 1], a, prow, t0, c + 1, pofs);
+      if (more && (c & 1) == 0) v[c >> 1] = load_row(t0 + kMacBlock, c >> 1);
+      // keep the loads together and ahead of this chunk's products
+      __builtin_amdgcn_sched_barrier(0);
+      if (active) {
+        sub_chunk_products<Uniform>(part, wbuf[c & 1], xs, c, lane);
+        // 8 products per partial sum when q < 2^60, otherwise 4 (ext_mac_tile_kernel)
+        if ((c & 1) || !Q60) {
+#pragma unroll
+          for (int k = 0; k < E; ++k)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) mac_fold(acc[k][p], part[k][p]);
+        }
+      }
+    }
+    if (active) {
+      // a tail block may stop between folds; the block's sum (at most 32 products and the carried
+      // residue, below 2^128) is reduced and carried on
+#pragma unroll
+      for (int k = 0; k < E; ++k)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          mac_fold(acc[k][p], part[k][p]);
+          acc[k][p] = u128{barrett_reduce_128(acc[k][p], q, r0, r1), 0};
+        }
+    }
+  }
+  if (active) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      mac_u64x2 r;
+      r.x = acc[0][p].lo;
+      r.y = acc[1][p].lo;
+      *(__attribute__((address_space(1))) mac_u64x2*)(reinterpret_cast<char*>(op + p * total + e0) + lofs) = r;
+    }
+  }
+}
+
+// ext_mac_plain_kernel with the plaintext word of element e of limb l at l (n >> log_g) + (e >> log_g)
+__global__ __launch_bounds__(kBlock) void ext_mac_sub_plain_kernel(MacArgs a, uint32_t log_n, uint32_t log_g,
+                                                                   size_t total) {
+  const uint32_t o = blockIdx.y;
+  uint64_t* const op = mac_out(a, o);
+  const size_t prow = static_cast<size_t>(o) * a.T;
+  const size_t n1 = (size_t(1) << log_n) - 1;
+  for (size_t e = blockIdx.x * (size_t)kBlock + threadIdx.x; e < total; e += (size_t)gridDim.x * kBlock) {
+    const int l = static_cast<int>(e >> log_n);
+    const int row = l < static_cast<int>(a.Ql) ? l : static_cast<int>(a.size_Q) + (l - static_cast<int>(a.Ql));
+    const uint64_t q = a.q[row], r0 = a.barrett[2 * row], r1 = a.barrett[2 * row + 1];
+    const size_t poff = (static_cast<size_t>(l) << (log_n - log_g)) + ((e & n1) >> log_g);
+    u128 acc[2] = {{0, 0}, {0, 0}};
+    if (a.accumulate) {
+      acc[0].lo = op[e];
+      acc[1].lo = op[total + e];
+    }
+    for (uint32_t t0 = 0; t0 < a.T; t0 += kMacChunk) {
+      const uint32_t cnt = min(a.T - t0, static_cast<uint32_t>(kMacChunk));
+      MacPart part[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+      for (uint32_t j = 0; j < cnt; ++j) {
+        const uint64_t* in = mac_in(a, t0 + j);
+        const uint64_t w = mac_pt(a, prow + t0 + j)[poff];
+        const uint32_t wl = static_cast<uint32_t>(w & kM30), wh = static_cast<uint32_t>(w >> 30);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const uint64_t x = in[p * total + e];
+          const uint32_t xl = static_cast<uint32_t>(x & kM30), xh = static_cast<uint32_t>(x >> 30);
+          part[p].ll += static_cast<uint64_t>(xl) * wl;
+          part[p].m1 += static_cast<uint64_t>(xl) * wh;
+          part[p].m2 += static_cast<uint64_t>(xh) * wl;
+          part[p].hh += static_cast<uint64_t>(xh) * wh;
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        mac_fold(acc[p], part[p]);
+        if ((t0 + kMacChunk) % kMacBlock == 0) acc[p] = u128{barrett_reduce_128(acc[p], q, r0, r1), 0};
+      }
+    }
+    op[e] = barrett_reduce_128(acc[0], q, r0, r1);
+    op[total + e] = barrett_reduce_128(acc[1], q, r0, r1);
+  }
+}
+
 // thread i: slot i % ns of term first + i / ns
 __global__ __launch_bounds__(kBlock) void conv_weight_slots_kernel(ConvShape c, const double* W, size_t first, size_t total,
                                                                    uint32_t log_ns, double2* out) {
@@ -275,6 +485,39 @@ hipError_t ext_mac(const MacArgs& a, size_t n, hipStream_t s) {
   } else {
     if (a.O > 65535) return hipErrorInvalidValue;
     ext_mac_plain_kernel<<<dim3(grid_for(total), a.O), kBlock, 0, s>>>(a, log_n, total);
+  }
+  return hipGetLastError();
+}
+
+hipError_t ext_mac_sub(const MacArgs& a, size_t n, size_t sub_degree, hipStream_t s) {
+  if (a.T == 0 || a.O == 0 || n == 0 || (n & (n - 1))) return hipErrorInvalidValue;
+  if (sub_degree == 0 || sub_degree > n || (sub_degree & (sub_degree - 1))) return hipErrorInvalidValue;
+  if ((!a.ins && !a.in0) || (!a.pts && !a.pt0) || (!a.outs && !a.out0)) return hipErrorInvalidValue;
+  const size_t total = static_cast<size_t>(a.Ql + a.P) * n;
+  const uint32_t log_n = static_cast<uint32_t>(__builtin_ctzll(n));
+  const uint32_t log_g = log_n - static_cast<uint32_t>(__builtin_ctzll(sub_degree));
+  if (log_g == 0) return ext_mac(a, n, s);  // full-size plaintexts: two words per lane, ext_mac's form
+  if (n >= kMacTileMinN && n % kMacTile == 0) {
+    // a tile never crosses a limb, and a limb holds a multiple of 8 tiles (n >= 1024 = 8 tiles), which
+    // the kernel's numbering of workgroups relies on
+    static_assert(kMacTileMinN % (8 * kMacTile) == 0, "a limb must hold a multiple of 8 tiles");
+    const size_t tiles = total / kMacTile, rows = (a.O + kSubWaves - 1) / kSubWaves;
+    if (tiles * rows > 0x7fffffffu) return hipErrorInvalidValue;
+    const dim3 grid(static_cast<unsigned>(tiles * rows));
+    const uint32_t r = static_cast<uint32_t>(rows);
+    const bool uniform = (size_t(1) << log_g) >= static_cast<size_t>(kMacTile);  // one word per tile
+#define PHX_SUB_LAUNCH(Q, U) ext_mac_sub_tile_kernel<Q, U><<<grid, 64 * kSubWaves, 0, s>>>(a, log_n, log_g, r, total)
+    if (a.q60) {
+      if (uniform) PHX_SUB_LAUNCH(true, true);
+      else PHX_SUB_LAUNCH(true, false);
+    } else {
+      if (uniform) PHX_SUB_LAUNCH(false, true);
+      else PHX_SUB_LAUNCH(false, false);
+    }
+#undef PHX_SUB_LAUNCH
+  } else {
+    if (a.O > 65535) return hipErrorInvalidValue;
+    ext_mac_sub_plain_kernel<<<dim3(grid_for(total), a.O), kBlock, 0, s>>>(a, log_n, log_g, total);
   }
   return hipGetLastError();
 }

@@ -146,36 +146,73 @@ const uint64_t* PhantomContext::monomial_ntt(uint32_t power, size_t L) const {
   return monomials_.emplace(key, std::move(d)).first->second.get();
 }
 
+// the embedding tables of ring degree n (the caller holds cache_mu_)
+void PhantomContext::build_embed(size_t n, DeviceBuffer<double2>& zeta_out, DeviceBuffer<uint32_t>& slot_of_out) const {
+  const size_t m = 2 * n;
+  std::vector<double2> zeta(m);
+  for (size_t j = 0; j < m; ++j) {
+    const double a = 2.0 * M_PI * static_cast<double>(j) / static_cast<double>(m);
+    zeta[j] = make_double2(std::cos(a), std::sin(a));
+  }
+  // position (5^j mod 2n - 1) / 2 holds slot j, its mirror n - 1 - that the conjugate
+  std::vector<uint32_t> slot_of(n);
+  uint64_t p = 1;
+  for (size_t j = 0; j < n / 2; ++j) {
+    const size_t idx = static_cast<size_t>((p - 1) / 2);
+    slot_of[idx] = static_cast<uint32_t>(j);
+    slot_of[n - 1 - idx] = static_cast<uint32_t>(j) | phx::EmbedTables::kConjBit;
+    p = (p * 5) % m;
+  }
+  DeviceBuffer<uint32_t> d;
+  d.upload(slot_of, stream_.s);
+  slot_of_out = std::move(d);
+  DeviceBuffer<double2> z;
+  z.upload(zeta, stream_.s);
+  zeta_out = std::move(z);
+}
+
 phx::EmbedTables PhantomContext::embed_tables() const {
   std::lock_guard<std::mutex> lk(cache_mu_);
-  if (!embed_zeta_) {
-    const size_t m = 2 * n_;
-    std::vector<double2> zeta(m);
-    for (size_t j = 0; j < m; ++j) {
-      const double a = 2.0 * M_PI * static_cast<double>(j) / static_cast<double>(m);
-      zeta[j] = make_double2(std::cos(a), std::sin(a));
-    }
-    // position (5^j mod 2n - 1) / 2 holds slot j, its mirror n - 1 - that the conjugate
-    std::vector<uint32_t> slot_of(n_);
-    uint64_t p = 1;
-    for (size_t j = 0; j < n_ / 2; ++j) {
-      const size_t idx = static_cast<size_t>((p - 1) / 2);
-      slot_of[idx] = static_cast<uint32_t>(j);
-      slot_of[n_ - 1 - idx] = static_cast<uint32_t>(j) | phx::EmbedTables::kConjBit;
-      p = (p * 5) % m;
-    }
-    DeviceBuffer<uint32_t> d;
-    d.upload(slot_of, stream_.s);
-    embed_slot_of_ = std::move(d);
-    DeviceBuffer<double2> z;
-    z.upload(zeta, stream_.s);
-    embed_zeta_ = std::move(z);
-  }
+  if (!embed_zeta_) build_embed(n_, embed_zeta_, embed_slot_of_);
   phx::EmbedTables t;
   t.n = n_;
   t.log_n = arith::log2_exact(n_);
   t.zeta = embed_zeta_.get();
   t.slot_of = embed_slot_of_.get();
+  return t;
+}
+
+void PhantomContext::check_sub_degree(size_t sub_degree) const {
+  if (sub_degree < 8 || sub_degree > n_ || (sub_degree & (sub_degree - 1)))
+    throw std::invalid_argument("the subring degree must be a power of two in [8, N]");
+}
+
+const phx::NttTables& PhantomContext::sub_ntt_tables(size_t sub_degree) const {
+  check_sub_degree(sub_degree);
+  if (sub_degree == n_) return ntt_->get();
+  std::lock_guard<std::mutex> lk(cache_mu_);
+  auto it = sub_ntt_.find(sub_degree);
+  if (it == sub_ntt_.end()) {
+    // root psi_N^(N/M) per modulus: the subring's twiddles are the first M of the context's
+    const std::vector<uint64_t>& psi = ntt_->roots();
+    std::vector<uint64_t> roots(qp_.size());
+    for (size_t i = 0; i < qp_.size(); ++i) roots[i] = arith::pow_mod(psi[i], n_ / sub_degree, qp_[i]);
+    it = sub_ntt_.emplace(sub_degree, std::make_unique<DeviceNttTables>(sub_degree, qp_, roots, stream_.s)).first;
+  }
+  return it->second->get();
+}
+
+phx::EmbedTables PhantomContext::sub_embed_tables(size_t sub_degree) const {
+  check_sub_degree(sub_degree);
+  if (sub_degree == n_) return embed_tables();
+  std::lock_guard<std::mutex> lk(cache_mu_);
+  SubEmbed& e = sub_embed_[sub_degree];
+  if (!e.zeta) build_embed(sub_degree, e.zeta, e.slot_of);
+  phx::EmbedTables t;
+  t.n = sub_degree;
+  t.log_n = arith::log2_exact(sub_degree);
+  t.zeta = e.zeta.get();
+  t.slot_of = e.slot_of.get();
   return t;
 }
 

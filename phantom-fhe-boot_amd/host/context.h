@@ -183,6 +183,15 @@ class PhantomContext {
   // basis.  The first use uploads on the context's own stream and waits for it.
   phx::EmbedTables embed_tables() const;
   phx::ComposeTables compose_tables(size_t chain_index) const;
+  // The subring Z[X^(N/M)] / (X^N + 1) of degree M = sub_degree (a power of two in [8, N]): a
+  // polynomial p(X) = p'(X^g), g = N / M, has NTT_N(p)[i] = NTT'_M(p')[i >> log2 g] in the engine's
+  // bit-reversed order, NTT'_M the size-M negacyclic transform with root psi_N^g per modulus (its
+  // twiddle table is the first M entries of the size-N one).  sub_ntt_tables: that transform's
+  // tables over the whole Q u P chain, rows as gpu_rns_tables(); sub_embed_tables: the degree-M
+  // embedding's, as a context of degree M builds them.  Built on first use and cached per M as the
+  // Galois permutations are; M = N gives the context's own tables.
+  const phx::NttTables& sub_ntt_tables(size_t sub_degree) const;
+  phx::EmbedTables sub_embed_tables(size_t sub_degree) const;
 
   // Opt-in mean-unbiased moddowns at every level (RnsTool::set_unbias): off by default, where each
   // division is the reference's bit for bit.  PHX_UNBIASED_MODDOWN=1 in the environment turns it
@@ -205,6 +214,14 @@ class PhantomContext {
   mutable std::map<std::pair<uint32_t, size_t>, DeviceBuffer<uint64_t>> monomials_;
   mutable DeviceBuffer<double2> embed_zeta_;
   mutable DeviceBuffer<uint32_t> embed_slot_of_;
+  struct SubEmbed {
+    DeviceBuffer<double2> zeta;
+    DeviceBuffer<uint32_t> slot_of;
+  };
+  void check_sub_degree(size_t sub_degree) const;
+  void build_embed(size_t degree, DeviceBuffer<double2>& zeta, DeviceBuffer<uint32_t>& slot_of) const;
+  mutable std::map<size_t, std::unique_ptr<DeviceNttTables>> sub_ntt_;  // per subring degree
+  mutable std::map<size_t, SubEmbed> sub_embed_;
   mutable std::map<size_t, DeviceBuffer<uint64_t>> compose_;  // per chain index, see compose_tables
   DeviceBuffer<uint64_t> ones_ntt_;  // NTT(1, ..., 1) over Q, for the unbiased moddown
   bool unbiased_ = false;

@@ -61,27 +61,28 @@ phx::MacArgs mac_args(const PhantomContext& ctx, size_t chain_index) {
   return a;
 }
 
-void conv2d_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, const phx::ConvShape& c,
-                const double* dev_W, double pt_scale, const uint64_t* const* const* evk, const uint32_t* galois_elts,
-                size_t group, uint64_t* const* outs, int* dev_overflow, hipStream_t s) {
-  if (!cts || !dev_W || !evk || !galois_elts || !outs) throw std::invalid_argument("null pointer");
-  if (!(pt_scale > 0)) throw std::invalid_argument("scale must be positive");
-  phx::MacArgs ma = mac_args(ctx, chain_index);  // checks the chain index and the special primes
-  const size_t n = ctx.poly_degree();
-  (void)conv_shape(n, c.width, c.slotstr, c.kernel, c.in_ch, c.out_ch);
-  const RnsTool& rt = ctx.get_context_data(chain_index).gpu_rns_tool();
-  const size_t Ql = rt.size_Ql(), QlP = Ql + ctx.size_P(), beta = rt.beta();
-  const size_t K2 = static_cast<size_t>(c.kernel) * c.kernel, T = c.in_ch * K2, ns = c.slots();
-  const size_t centre = K2 / 2;
+namespace {
+
+// the operand checks conv2d_raw and conv2d_apply share, before anything is enqueued
+void check_operands(const phx::ConvShape& c, const uint64_t* const* cts, const uint64_t* const* const* evk,
+                    uint64_t* const* outs) {
+  const size_t K2 = static_cast<size_t>(c.kernel) * c.kernel;
   for (size_t k = 0; k < c.in_ch; ++k)
     if (!cts[k]) throw std::invalid_argument("null input channel");
   for (size_t h = 0; h < c.out_ch; ++h)
     if (!outs[h]) throw std::invalid_argument("null output channel");
   for (size_t t = 0; t < K2; ++t)
-    if (!evk[t] && t != centre) throw std::invalid_argument("conv: only the centre tap goes without a rotation key");
-  if (group == 0) group = conv_group(ctx, chain_index, c);
-  group = std::min<size_t>(group, c.out_ch);
-  const size_t ext_words = 2 * QlP * n, pt_words = QlP * n, ct_words = 2 * Ql * n;
+    if (!evk[t] && t != K2 / 2) throw std::invalid_argument("conv: only the centre tap goes without a rotation key");
+}
+
+// every rotation of every input channel in the extended basis: term (k, tap) at
+// rots + (k K^2 + tap) ext_words (in_ch modups and batched rotation launches)
+void conv_rotate(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, const phx::ConvShape& c,
+                 const uint64_t* const* const* evk, const uint32_t* galois_elts, uint64_t* rots, hipStream_t s) {
+  const size_t n = ctx.poly_degree();
+  const RnsTool& rt = ctx.get_context_data(chain_index).gpu_rns_tool();
+  const size_t Ql = rt.size_Ql(), QlP = Ql + ctx.size_P(), beta = rt.beta();
+  const size_t K2 = static_cast<size_t>(c.kernel) * c.kernel, ext_words = 2 * QlP * n;
   const phx::NttTables& ntt = ctx.gpu_rns_tables();
 
   // the K^2 rotations' entries, the same for every input channel (outputs tap ext_words apart)
@@ -104,8 +105,7 @@ void conv2d_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* c
     hip_ok(phx::write_words(table.get() + w0, w, cnt, s), "conv rotation table");
   }
 
-  // every rotation of every input channel in the extended basis: term (k, tap) at rots + (k K^2 + tap) ext_words
-  DeviceBuffer<uint64_t> rots(T * ext_words, s), digits(beta * QlP * n, s);
+  DeviceBuffer<uint64_t> digits(beta * QlP * n, s);
   phx::KsRotateBatchArgs ba;
   ba.digits = digits.get();
   ba.entries = reinterpret_cast<const phx::KsBatchEntry*>(table.get());
@@ -122,9 +122,58 @@ void conv2d_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* c
   for (size_t k = 0; k < c.in_ch; ++k) {
     rt.modup(digits.get(), cts[k] + Ql * n, ntt, s);
     ba.ct = cts[k];
-    ba.out = rots.get() + k * K2 * ext_words;
+    ba.out = rots + k * K2 * ext_words;
     hip_ok(phx::keyswitch_rotate_batch(ba, n, s), "conv rotations");
   }
+}
+
+// moddown of the 2 out_ch output polynomials in acc ([out_ch][2][Ql + P][n]) to outs
+void conv_moddown(const PhantomContext& ctx, size_t chain_index, const phx::ConvShape& c, uint64_t* acc,
+                  uint64_t* const* outs, hipStream_t s) {
+  const size_t n = ctx.poly_degree();
+  const RnsTool& rt = ctx.get_context_data(chain_index).gpu_rns_tool();
+  const size_t Ql = rt.size_Ql(), QlP = Ql + ctx.size_P();
+  const size_t ext_words = 2 * QlP * n, ct_words = 2 * Ql * n;
+  const phx::NttTables& ntt = ctx.gpu_rns_tables();
+  // 8 polynomials per launch set (the fused conversion's batch)
+  const bool contiguous = [&] {
+    for (size_t h = 1; h < c.out_ch; ++h)
+      if (outs[h] != outs[0] + h * ct_words) return false;
+    return true;
+  }();
+  DeviceBuffer<uint64_t> stage;
+  if (!contiguous) stage.allocate(c.out_ch * ct_words, s);
+  uint64_t* const dst = contiguous ? outs[0] : stage.get();
+  constexpr size_t kPer = 4;  // output channels per moddown
+  for (size_t h0 = 0; h0 < c.out_ch; h0 += kPer) {
+    const size_t g = std::min(kPer, c.out_ch - h0);
+    rt.moddown_add(dst + h0 * ct_words, acc + h0 * ext_words, false, ntt, s, 2 * g);
+  }
+  if (!contiguous)
+    for (size_t h = 0; h < c.out_ch; ++h)
+      PHX_CHECK(hipMemcpyAsync(outs[h], stage.get() + h * ct_words, ct_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+}
+
+}  // namespace
+
+void conv2d_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, const phx::ConvShape& c,
+                const double* dev_W, double pt_scale, const uint64_t* const* const* evk, const uint32_t* galois_elts,
+                size_t group, uint64_t* const* outs, int* dev_overflow, hipStream_t s) {
+  if (!cts || !dev_W || !evk || !galois_elts || !outs) throw std::invalid_argument("null pointer");
+  if (!(pt_scale > 0)) throw std::invalid_argument("scale must be positive");
+  phx::MacArgs ma = mac_args(ctx, chain_index);  // checks the chain index and the special primes
+  const size_t n = ctx.poly_degree();
+  (void)conv_shape(n, c.width, c.slotstr, c.kernel, c.in_ch, c.out_ch);
+  const RnsTool& rt = ctx.get_context_data(chain_index).gpu_rns_tool();
+  const size_t QlP = rt.size_Ql() + ctx.size_P();
+  const size_t K2 = static_cast<size_t>(c.kernel) * c.kernel, T = c.in_ch * K2, ns = c.slots();
+  check_operands(c, cts, evk, outs);
+  if (group == 0) group = conv_group(ctx, chain_index, c);
+  group = std::min<size_t>(group, c.out_ch);
+  const size_t ext_words = 2 * QlP * n, pt_words = QlP * n;
+
+  DeviceBuffer<uint64_t> rots(T * ext_words, s);
+  conv_rotate(ctx, chain_index, cts, c, evk, galois_elts, rots.get(), s);
 
   // inner sums, `group` output channels per pass
   DeviceBuffer<uint64_t> acc(c.out_ch * ext_words, s), pts(group * T * pt_words, s);
@@ -144,24 +193,71 @@ void conv2d_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* c
     ma.O = static_cast<uint32_t>(g);
     hip_ok(phx::ext_mac(ma, n, s), "conv inner sums");
   }
+  conv_moddown(ctx, chain_index, c, acc.get(), outs, s);
+}
 
-  // moddown of the 2 out_ch output polynomials, 8 per launch set (the fused conversion's batch)
-  const bool contiguous = [&] {
-    for (size_t h = 1; h < c.out_ch; ++h)
-      if (outs[h] != outs[0] + h * ct_words) return false;
-    return true;
-  }();
-  DeviceBuffer<uint64_t> stage;
-  if (!contiguous) stage.allocate(c.out_ch * ct_words, s);
-  uint64_t* const dst = contiguous ? outs[0] : stage.get();
-  constexpr size_t kPer = 4;  // output channels per moddown
-  for (size_t h0 = 0; h0 < c.out_ch; h0 += kPer) {
-    const size_t g = std::min(kPer, c.out_ch - h0);
-    rt.moddown_add(dst + h0 * ct_words, acc.get() + h0 * ext_words, false, ntt, s, 2 * g);
+// ---- prepared layers ---------------------------------------------------------------------------
+
+ConvPlanData::~ConvPlanData() {
+  if (pts) (void)hipFree(pts);
+}
+
+std::unique_ptr<ConvPlanData> conv2d_prepare(const PhantomContext& ctx, size_t chain_index, const phx::ConvShape& c,
+                                             const double* dev_W, double pt_scale, int* dev_overflow, hipStream_t s) {
+  if (!dev_W) throw std::invalid_argument("null pointer");
+  if (!(pt_scale > 0)) throw std::invalid_argument("scale must be positive");
+  const phx::MacArgs ma = mac_args(ctx, chain_index);  // checks the chain index and the special primes
+  const size_t n = ctx.poly_degree();
+  (void)conv_shape(n, c.width, c.slotstr, c.kernel, c.in_ch, c.out_ch);
+  const size_t ns = c.slots(), M = 2 * ns, terms = c.terms(), QlP = static_cast<size_t>(ma.Ql) + ma.P;
+  if (M < 8) throw std::invalid_argument("conv plan: fewer than 4 slots");
+  (void)ctx.sub_ntt_tables(M);  // built (first use) before anything is enqueued
+  auto plan = std::make_unique<ConvPlanData>();
+  plan->ctx = &ctx;
+  plan->chain_index = chain_index;
+  plan->shape = c;
+  plan->scale = pt_scale;
+  plan->sub_degree = M;
+  plan->words = terms * QlP * M;
+  PHX_CHECK(hipMalloc(&plan->pts, plan->words * sizeof(uint64_t)));
+  // slices of terms that bound the slot vectors' scratch (16 MiB)
+  const size_t slice = std::max<size_t>(1, (size_t(1) << 20) / ns);
+  DeviceBuffer<double> slots(std::min(slice, terms) * ns * 2, s);
+  for (size_t t0 = 0; t0 < terms; t0 += slice) {
+    const size_t cnt = std::min(slice, terms - t0);
+    hip_ok(phx::conv_weight_slots(c, dev_W, t0, cnt, slots.get(), s), "conv weight slots");
+    encode_sub_raw(ctx, chain_index, true, reinterpret_cast<const std::complex<double>*>(slots.get()), ns, ns, pt_scale,
+                   cnt, plan->pts + t0 * QlP * M, dev_overflow, s);
   }
-  if (!contiguous)
-    for (size_t h = 0; h < c.out_ch; ++h)
-      PHX_CHECK(hipMemcpyAsync(outs[h], stage.get() + h * ct_words, ct_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+  PHX_CHECK(hipStreamSynchronize(s));  // dev_W is the caller's again, and the plan is complete
+  return plan;
+}
+
+void conv2d_apply(const PhantomContext& ctx, const ConvPlanData& plan, const uint64_t* const* cts,
+                  const uint64_t* const* const* evk, const uint32_t* galois_elts, uint64_t* const* outs,
+                  hipStream_t s) {
+  if (!cts || !evk || !galois_elts || !outs) throw std::invalid_argument("null pointer");
+  if (plan.ctx != &ctx) throw std::invalid_argument("conv plan: prepared for another context");
+  const phx::ConvShape& c = plan.shape;
+  phx::MacArgs ma = mac_args(ctx, plan.chain_index);
+  const size_t n = ctx.poly_degree();
+  const size_t QlP = static_cast<size_t>(ma.Ql) + ma.P;
+  const size_t K2 = static_cast<size_t>(c.kernel) * c.kernel, T = c.in_ch * K2;
+  check_operands(c, cts, evk, outs);
+  const size_t ext_words = 2 * QlP * n;
+
+  DeviceBuffer<uint64_t> rots(T * ext_words, s), acc(c.out_ch * ext_words, s);
+  conv_rotate(ctx, plan.chain_index, cts, c, evk, galois_elts, rots.get(), s);
+  ma.in0 = rots.get();
+  ma.in_stride = ext_words;
+  ma.pt0 = plan.pts;
+  ma.pt_stride = QlP * plan.sub_degree;
+  ma.out0 = acc.get();
+  ma.out_stride = ext_words;
+  ma.T = static_cast<uint32_t>(T);
+  ma.O = c.out_ch;
+  hip_ok(phx::ext_mac_sub(ma, n, plan.sub_degree, s), "conv inner sums");
+  conv_moddown(ctx, plan.chain_index, c, acc.get(), outs, s);
 }
 
 }  // namespace phantom

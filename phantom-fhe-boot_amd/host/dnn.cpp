@@ -4,6 +4,7 @@
 #include <cmath>
 #include <complex>
 #include <stdexcept>
+#include <string>
 #include <unordered_set>
 
 #include "buffer.h"
@@ -81,21 +82,29 @@ DNN::Tensor3 DNN::DecTensor(const TensorCT& t, PhantomSecretKey& sk) {
   return out;
 }
 
-TensorCT DNN::Conv(const TensorCT& input, const Weight4& weight, size_t stride) {
+std::vector<double> DNN::flatten_weight(const Weight4& weight, size_t& K, size_t& in_ch, size_t& out_ch,
+                                        const char* who) {
+  const std::string name(who);
   if (weight.empty() || weight[0].size() != weight.size() || weight[0][0].empty() || weight[0][0][0].empty())
-    throw std::invalid_argument("Conv: weight must be [K][K][in_ch][out_ch]");
-  const size_t K = weight.size(), in_ch = weight[0][0].size(), out_ch = weight[0][0][0].size();
+    throw std::invalid_argument(name + ": weight must be [K][K][in_ch][out_ch]");
+  K = weight.size(), in_ch = weight[0][0].size(), out_ch = weight[0][0][0].size();
   std::vector<double> w(K * K * in_ch * out_ch);
   for (size_t a = 0; a < K; ++a) {
-    if (weight[a].size() != K) throw std::invalid_argument("Conv: weight must be [K][K][in_ch][out_ch]");
+    if (weight[a].size() != K) throw std::invalid_argument(name + ": weight must be [K][K][in_ch][out_ch]");
     for (size_t b = 0; b < K; ++b) {
-      if (weight[a][b].size() != in_ch) throw std::invalid_argument("Conv: ragged weight");
+      if (weight[a][b].size() != in_ch) throw std::invalid_argument(name + ": ragged weight");
       for (size_t k = 0; k < in_ch; ++k) {
-        if (weight[a][b][k].size() != out_ch) throw std::invalid_argument("Conv: ragged weight");
+        if (weight[a][b][k].size() != out_ch) throw std::invalid_argument(name + ": ragged weight");
         for (size_t h = 0; h < out_ch; ++h) w[((a * K + b) * in_ch + k) * out_ch + h] = weight[a][b][k][h];
       }
     }
   }
+  return w;
+}
+
+TensorCT DNN::Conv(const TensorCT& input, const Weight4& weight, size_t stride) {
+  size_t K, in_ch, out_ch;
+  const std::vector<double> w = flatten_weight(weight, K, in_ch, out_ch, "Conv");
   if (in_ch != input.num_ch_) throw std::invalid_argument("Conv: the weight's input channels differ from the tensor's");
   DeviceBuffer<double> dW;
   dW.upload(w, context_.stream());
@@ -103,10 +112,53 @@ TensorCT DNN::Conv(const TensorCT& input, const Weight4& weight, size_t stride) 
 }
 
 TensorCT DNN::Conv(const TensorCT& input, const double* dev_W, size_t kernel_h, size_t out_ch, size_t stride) {
+  return conv_run(input, dev_W, nullptr, kernel_h, out_ch, stride);
+}
+
+DNN::ConvPlan::ConvPlan(ConvPlan&&) noexcept = default;
+DNN::ConvPlan& DNN::ConvPlan::operator=(ConvPlan&&) noexcept = default;
+DNN::ConvPlan::~ConvPlan() = default;
+size_t DNN::ConvPlan::width() const { return data_->shape.width; }
+size_t DNN::ConvPlan::slotstr() const { return data_->shape.slotstr; }
+size_t DNN::ConvPlan::kernel() const { return data_->shape.kernel; }
+size_t DNN::ConvPlan::in_ch() const { return data_->shape.in_ch; }
+size_t DNN::ConvPlan::out_ch() const { return data_->shape.out_ch; }
+size_t DNN::ConvPlan::chain_index() const { return data_->chain_index; }
+double DNN::ConvPlan::scale() const { return data_->scale; }
+size_t DNN::ConvPlan::bytes() const { return data_->bytes(); }
+
+DNN::ConvPlan DNN::PrepareConv(const Weight4& weight, size_t width, size_t slotstr, size_t chain_index) {
+  size_t K, in_ch, out_ch;
+  const std::vector<double> w = flatten_weight(weight, K, in_ch, out_ch, "PrepareConv");
+  DeviceBuffer<double> dW;
+  dW.upload(w, context_.stream());
+  return PrepareConv(dW.get(), K, in_ch, out_ch, width, slotstr, chain_index);
+}
+
+DNN::ConvPlan DNN::PrepareConv(const double* dev_W, size_t kernel_h, size_t in_ch, size_t out_ch, size_t width,
+                               size_t slotstr, size_t chain_index) {
+  if (!dev_W) throw std::invalid_argument("PrepareConv: null weights");
+  const phx::ConvShape shape = conv_shape(context_.poly_degree(), width, slotstr, kernel_h, in_ch, out_ch);
+  hipStream_t s = context_.stream();
+  DeviceBuffer<int> flag(1, s);
+  PHX_CHECK(hipMemsetAsync(flag.get(), 0, sizeof(int), s));
+  ConvPlan plan;
+  plan.data_ = conv2d_prepare(context_, chain_index, shape, dev_W, static_cast<double>(scale_), flag.get(), s);
+  if (flag.download(s)[0]) throw std::invalid_argument("PrepareConv: encoded weights are too large");
+  return plan;
+}
+
+TensorCT DNN::Conv(const TensorCT& input, const ConvPlan& plan, size_t stride) {
+  if (!plan) throw std::invalid_argument("Conv: empty plan");
+  return conv_run(input, nullptr, plan.data_.get(), plan.kernel(), plan.out_ch(), stride);
+}
+
+TensorCT DNN::conv_run(const TensorCT& input, const double* dev_W, const ConvPlanData* plan, size_t kernel_h,
+                       size_t out_ch, size_t stride) {
   if (stride != 1 && stride != 2) throw std::invalid_argument("Conv: stride must be 1 or 2");
   const size_t in_ch = input.num_ch_, n = context_.poly_degree();
   if (in_ch == 0 || input.ctks_.size() != in_ch) throw std::invalid_argument("Conv: channel count mismatch");
-  if (!dev_W) throw std::invalid_argument("Conv: null weights");
+  if (!dev_W && !plan) throw std::invalid_argument("Conv: null weights");
   const PhantomCiphertext& first = input.ctks_[0];
   for (const PhantomCiphertext& c : input.ctks_)
     if (c.size() != 2 || c.chain_index() != first.chain_index() || c.scale() != first.scale() ||
@@ -121,6 +173,14 @@ TensorCT DNN::Conv(const TensorCT& input, const double* dev_W, size_t kernel_h, 
   }
   const std::vector<PhantomCiphertext>& in = rescaled.empty() ? input.ctks_ : rescaled;
   const size_t chain = in[0].chain_index();
+  if (plan) {
+    const phx::ConvShape& p = plan->shape;
+    if (plan->ctx != &context_) throw std::invalid_argument("Conv: the plan was prepared for another context");
+    if (p.width != input.width_ || p.slotstr != input.slotstr_ || p.in_ch != in_ch)
+      throw std::invalid_argument("Conv: the plan's geometry or channel count differs from the tensor's");
+    if (plan->chain_index != chain)
+      throw std::invalid_argument("Conv: the plan was prepared at another chain index than the input's");
+  }
 
   const std::vector<int> rots = conv_rotations(input.width_, input.slotstr_, kernel_h);
   std::vector<const uint64_t* const*> evk(rots.size(), nullptr);
@@ -151,9 +211,13 @@ TensorCT DNN::Conv(const TensorCT& input, const double* dev_W, size_t kernel_h, 
     o.set_asymmetric(in[0].is_asymmetric());
     outs[h] = o.data();
   }
-  encoder_.set_sparse_encode(2 * shape.slots());
-  conv2d_raw(context_, chain, cts.data(), shape, dev_W, static_cast<double>(scale_), evk.data(), elts.data(), 0,
-             outs.data(), nullptr, s);
+  if (plan) {
+    conv2d_apply(context_, *plan, cts.data(), evk.data(), elts.data(), outs.data(), s);
+  } else {
+    encoder_.set_sparse_encode(2 * shape.slots());
+    conv2d_raw(context_, chain, cts.data(), shape, dev_W, static_cast<double>(scale_), evk.data(), elts.data(), 0,
+               outs.data(), nullptr, s);
+  }
   return result;
 }
 

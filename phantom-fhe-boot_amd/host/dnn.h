@@ -9,6 +9,7 @@
 #pragma once
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "ciphertext.h"
@@ -18,6 +19,8 @@
 #include "keys.h"
 
 namespace phantom {
+
+struct ConvPlanData;  // host/conv2d.h
 
 // one ciphertext per channel: a width_ x width_ image in (width_ 2^slotstr_)^2 sparse-packed slots,
 // pixel (r, c) at slot (r width_ 2^slotstr_ + c) 2^slotstr_ (include/dnn.cuh:33-39)
@@ -71,6 +74,41 @@ class DNN {
   // the same with the weights already on the device: dev_W [K][K][in_ch][out_ch] doubles, complete
   // in the context's stream order
   TensorCT Conv(const TensorCT& input, const double* dev_W, size_t kernel_h, size_t out_ch, size_t stride);
+
+  // A prepared layer: the weights of one layer geometry at one chain index, encoded once in the
+  // compact subring form (host/conv2d.h) at scale_ and kept on the device.  Move-only; it must not
+  // outlive the context, and no Conv using it may be in flight when it is destroyed.
+  class ConvPlan {
+   public:
+    ConvPlan() = default;
+    ConvPlan(ConvPlan&&) noexcept;
+    ConvPlan& operator=(ConvPlan&&) noexcept;
+    ~ConvPlan();
+    size_t width() const;
+    size_t slotstr() const;
+    size_t kernel() const;
+    size_t in_ch() const;
+    size_t out_ch() const;
+    size_t chain_index() const;
+    double scale() const;
+    size_t bytes() const;  // the plan's device size
+    explicit operator bool() const { return data_ != nullptr; }
+
+   private:
+    friend class DNN;
+    std::unique_ptr<ConvPlanData> data_;
+  };
+  // weight[a][b][k][h] for inputs of `width` x `width` pixels packed with `slotstr` at `chain_index`
+  // (the level the layer's input has after the rescale a degree-2 input gets).  Waits for the
+  // context's stream.
+  ConvPlan PrepareConv(const Weight4& weight, size_t width, size_t slotstr, size_t chain_index);
+  ConvPlan PrepareConv(const double* dev_W, size_t kernel_h, size_t in_ch, size_t out_ch, size_t width, size_t slotstr,
+                       size_t chain_index);
+  // Conv with the plan's weights: the metadata rules of Conv above, no encode.  std::invalid_argument
+  // also when the plan's geometry, channel count or chain index differs from the input's (after the
+  // rescale).  The result equals Conv(weight) up to the plaintexts' rounding: the compact encoding
+  // rounds 2 ns coefficients, the full-size one N.
+  TensorCT Conv(const TensorCT& input, const ConvPlan& plan, size_t stride);
   // per channel a x + b with a = weight / sqrt(var + 1e-5), b = bias - a mean (src/dnn.cu:454-480)
   TensorCT BatchNorm(const TensorCT& input, const std::vector<double>& weight, const std::vector<double>& bias,
                      const std::vector<double>& mean, const std::vector<double>& var);
@@ -78,6 +116,12 @@ class DNN {
   TensorCT Add(const TensorCT& a, const TensorCT& b);
 
  private:
+  // the layer on dev_W (conv2d_raw), or on `plan` when it is not null (conv2d_apply)
+  TensorCT conv_run(const TensorCT& input, const double* dev_W, const ConvPlanData* plan, size_t kernel_h, size_t out_ch,
+                    size_t stride);
+  static std::vector<double> flatten_weight(const Weight4& weight, size_t& K, size_t& in_ch, size_t& out_ch,
+                                            const char* who);
+
   size_t scale_;
   PhantomGaloisKeyFused gk_;
   const PhantomContext& context_;

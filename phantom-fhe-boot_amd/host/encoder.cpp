@@ -389,6 +389,47 @@ void encode_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const s
   }
 }
 
+void encode_sub_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const std::complex<double>* values,
+                    size_t num_values, size_t sub_slots, double scale, size_t count, uint64_t* out, int* dev_overflow,
+                    hipStream_t s) {
+  if (!(scale > 0)) throw std::invalid_argument("scale must be positive");
+  const size_t n = ctx.poly_degree();
+  if (sub_slots > n / 2) throw std::invalid_argument("the subring degree must be a power of two in [8, N]");
+  const size_t M = 2 * sub_slots;
+  const phx::LimbMap map = encode_limb_map(ctx, chain_index, ext);
+  const phx::NttTables& ntt = ctx.sub_ntt_tables(M);  // checks M
+  if (num_values > sub_slots) throw std::invalid_argument("more values than slots");
+  if (count == 0) return;
+  if ((!values && num_values) || !out) throw std::invalid_argument("null pointer");
+  const phx::EmbedTables t = ctx.sub_embed_tables(M);
+  const size_t words = static_cast<size_t>(map.num_limbs) * M;
+  // slices of about the scratch a full-size slice takes
+  const size_t slice = kEncodeSlice * (n / M);
+  for (size_t p = 0; p < count; p += slice) {
+    const size_t c = std::min(slice, count - p);
+    DeviceBuffer<double2> work(c * M, s);
+    DeviceBuffer<double> coeffs(c * M, s);
+    enc_ok(phx::embed_inverse(t, reinterpret_cast<const double2*>(values) + p * num_values, num_values, 0,
+                              coeffs.get(), work.get(), c, s),
+           "embedding");
+    uint64_t* o = out + p * words;
+    enc_ok(phx::round_to_rns(ntt, coeffs.get(), scale, o, map, c, dev_overflow, s), "round and split");
+    enc_ok(phx::ntt_forward(ntt, o, o, map.batched(static_cast<int>(c)), s), "encode NTT");
+  }
+}
+
+void sub_ntt_raw(const PhantomContext& ctx, size_t chain_index, bool ext, size_t sub_degree, bool inverse,
+                 uint64_t* data, size_t count, hipStream_t s) {
+  const phx::LimbMap map = encode_limb_map(ctx, chain_index, ext);
+  const phx::NttTables& ntt = ctx.sub_ntt_tables(sub_degree);
+  if (count == 0) return;
+  if (!data) throw std::invalid_argument("null pointer");
+  if (count > 0x7fffffffu) throw std::invalid_argument("batch too large");
+  const phx::LimbMap m = map.batched(static_cast<int>(count));
+  if (inverse) enc_ok(phx::ntt_inverse(ntt, data, data, m, nullptr, nullptr, s), "subring INTT");
+  else enc_ok(phx::ntt_forward(ntt, data, data, m, s), "subring NTT");
+}
+
 void compose_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* plain,
                  const uint64_t* const* plains, size_t count, double mul, double* coeffs, hipStream_t s) {
   const phx::ComposeTables ct = ctx.compose_tables(chain_index);

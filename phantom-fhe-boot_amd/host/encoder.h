@@ -146,5 +146,18 @@ void encode_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const s
                 uint64_t* const* outs, int* dev_overflow, hipStream_t s);
 void decode_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* plain, const uint64_t* const* plains,
                 double scale, size_t count, std::complex<double>* values, hipStream_t s);
+// The compact sparse encoder (the reference's sparse path, src/ckks.cu:180-270: a size-ns FFT,
+// decompose_array over 2 ns coefficients, extend_sparse_ckks).  A plaintext whose sub_slots = ns
+// values tile every block of ns slots is p'(X^(N / 2 ns)) up to rounding; this writes p' alone:
+// values [count][num_values] (zero-padded to ns) -> out [count][limbs][M], M = 2 ns, the size-M
+// inverse embedding, round and split over M coefficients, and the size-M forward NTT of
+// PhantomContext::sub_ntt_tables(M).  Word e of the full-size NTT-form plaintext is word
+// e >> log2(N / M) of this one.  With ns = N / 2 it is encode_raw bit for bit.
+void encode_sub_raw(const PhantomContext& ctx, size_t chain_index, bool ext, const std::complex<double>* values,
+                    size_t num_values, size_t sub_slots, double scale, size_t count, uint64_t* out, int* dev_overflow,
+                    hipStream_t s);
+// the subring transform in place on data [count][limbs][sub_degree]; the inverse includes M^-1
+void sub_ntt_raw(const PhantomContext& ctx, size_t chain_index, bool ext, size_t sub_degree, bool inverse,
+                 uint64_t* data, size_t count, hipStream_t s);
 
 }  // namespace phantom

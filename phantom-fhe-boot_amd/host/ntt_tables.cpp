@@ -1,5 +1,6 @@
 #include "ntt_tables.h"
 
+#include <exception>
 #include <stdexcept>
 #include <thread>
 
@@ -10,12 +11,14 @@ namespace phantom {
 
 using namespace phantom::arith;
 
-HostNttTable make_host_ntt_table(size_t n, uint64_t q) {
+HostNttTable make_host_ntt_table(size_t n, uint64_t q, uint64_t root) {
   const int logn = log2_exact(n);
   if (logn < 0) throw std::invalid_argument("ring degree must be a power of two");
   HostNttTable h;
   h.q = q;
-  h.psi = minimal_primitive_root(2 * n, q);
+  if (root && (root >= q || pow_mod(root, n, q) != q - 1))
+    throw std::invalid_argument("not a primitive 2n-th root of unity");
+  h.psi = root ? root : minimal_primitive_root(2 * n, q);
   const uint64_t ipsi = inv_mod(h.psi, q);
   h.tw.resize(n); h.tw_shoup.resize(n); h.itw.resize(n); h.itw_shoup.resize(n);
   uint64_t p = 1, ip = 1;
@@ -36,8 +39,13 @@ HostNttTable make_host_ntt_table(size_t n, uint64_t q) {
 }
 
 DeviceNttTables::DeviceNttTables(size_t n, const std::vector<uint64_t>& moduli, hipStream_t stream)
+    : DeviceNttTables(n, moduli, {}, stream) {}
+
+DeviceNttTables::DeviceNttTables(size_t n, const std::vector<uint64_t>& moduli, const std::vector<uint64_t>& roots,
+                                 hipStream_t stream)
     : moduli_(moduli) {
   const size_t L = moduli.size();
+  if (!roots.empty() && roots.size() != L) throw std::invalid_argument("one root per modulus");
   t_.n = n;
   t_.log_n = log2_exact(n);
   t_.lazy16 = true;
@@ -52,12 +60,20 @@ DeviceNttTables::DeviceNttTables(size_t n, const std::vector<uint64_t>& moduli, 
     // table generation is O(n L) host work per context; spread it over a few threads
     const unsigned nt = std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u);
     std::vector<std::thread> th;
+    std::vector<std::exception_ptr> errs(nt);
     for (unsigned w = 0; w < nt; ++w)
       th.emplace_back([&, w] {
-        for (size_t i = w; i < L; i += nt) host[i] = make_host_ntt_table(n, moduli[i]);
+        try {
+          for (size_t i = w; i < L; i += nt) host[i] = make_host_ntt_table(n, moduli[i], roots.empty() ? 0 : roots[i]);
+        } catch (...) {
+          errs[w] = std::current_exception();
+        }
       });
     for (auto& x : th) x.join();
+    for (auto& e : errs)
+      if (e) std::rethrow_exception(e);
   }
+  for (const HostNttTable& h : host) roots_.push_back(h.psi);
   std::vector<uint64_t> flat(n * L), mod(L), bar(2 * L), ninv(L), ninvs(L);
   for (size_t i = 0; i < L; ++i) {
     mod[i] = moduli[i];

@@ -142,6 +142,16 @@ _SIGS = {
     "phantom_conv2d": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, sz, sz, sz, sz, vp, ctypes.c_double,
                                       ctypes.POINTER(ctypes.POINTER(vp)), sz, ctypes.POINTER(ctypes.c_uint32), sz,
                                       ctypes.POINTER(vp), vp, vp]),
+    "phantom_ckks_encode_sub": (ctypes.c_int, [vp, sz, ctypes.c_int, vp, sz, sz, ctypes.c_double, sz, vp, vp, vp]),
+    "phantom_sub_ntt": (ctypes.c_int, [vp, sz, ctypes.c_int, sz, ctypes.c_int, vp, sz, vp]),
+    "phantom_ext_mac_sub": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, vp, sz, sz, ctypes.POINTER(vp), ctypes.c_int,
+                                           vp]),
+    "phantom_conv2d_prepare": (ctypes.c_int, [vp, sz, sz, sz, sz, sz, sz, vp, ctypes.c_double, vp, vp,
+                                              ctypes.POINTER(vp)]),
+    "phantom_conv_plan_bytes": (ctypes.c_int, [vp, ctypes.POINTER(sz)]),
+    "phantom_conv_plan_destroy": (ctypes.c_int, [vp]),
+    "phantom_conv2d_apply": (ctypes.c_int, [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.POINTER(vp)), sz,
+                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(vp), vp]),
 }
 
 _lib = None
@@ -266,6 +276,16 @@ class Encoder:
 
     def decode(self, chain_index, plain, scale, values, stream, count=1):
         check(load().phantom_ckks_decode(self.ctx.handle, chain_index, plain, scale, count, values, stream))
+
+    def encode_sub(self, chain_index, values, num_values, sub_slots, scale, out, stream, ext=False, count=1,
+                   overflow=None):
+        """compact sparse plaintexts [count][limbs][2 sub_slots] (NTT form over the subring)"""
+        check(load().phantom_ckks_encode_sub(self.ctx.handle, chain_index, 1 if ext else 0, values, num_values,
+                                             sub_slots, scale, count, out, overflow, stream))
+
+    def sub_ntt(self, chain_index, sub_degree, data, stream, ext=False, inverse=False, count=1):
+        check(load().phantom_sub_ntt(self.ctx.handle, chain_index, 1 if ext else 0, sub_degree, 1 if inverse else 0,
+                                     data, count, stream))
 
 
 class Encryptor:
@@ -486,6 +506,53 @@ class Conv:
         width, slotstr, kernel, in_ch, out_ch = shape
         check(load().phantom_conv_weight_slots(width, slotstr, kernel, in_ch, out_ch, dev_W, first_term, count,
                                                dev_out, stream))
+
+    @staticmethod
+    def prepare(ctx, chain_index, shape, dev_W, pt_scale, stream, overflow=None):
+        """a ConvPlan: the layer's weights encoded once in the compact subring form, kept on the device"""
+        width, slotstr, kernel, in_ch, out_ch = shape
+        h = vp()
+        check(load().phantom_conv2d_prepare(ctx.handle, chain_index, in_ch, out_ch, width, slotstr, kernel, dev_W,
+                                            pt_scale, overflow, stream, ctypes.byref(h)))
+        return ConvPlan(h, shape)
+
+    @staticmethod
+    def apply(ctx, plan, cts, key_digits, dnum, galois_elts, outs, stream):
+        """cts / outs: ctypes arrays of device pointers; key_digits: array of K^2 arrays of dnum device
+        pointers (NULL at the centre tap); galois_elts: ctypes uint32 array"""
+        check(load().phantom_conv2d_apply(ctx.handle, plan.handle, cts, key_digits, dnum, galois_elts, outs, stream))
+
+
+class ConvPlan:
+    """Owning handle of a phantom_conv_plan (a device allocation of the layer's compact plaintexts):
+    close() it, or use it as a context manager.  No apply may be in flight when it is closed."""
+
+    def __init__(self, handle, shape):
+        self.handle = handle
+        self.shape = shape
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown: the library may be gone
+            pass
+
+    @property
+    def bytes(self):
+        b = sz(0)
+        check(load().phantom_conv_plan_bytes(self.handle, ctypes.byref(b)))
+        return b.value
+
+    def close(self):
+        if self.handle:
+            load().phantom_conv_plan_destroy(self.handle)
+            self.handle = None
 
 
 def ptr_array(ptrs):
