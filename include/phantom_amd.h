@@ -361,6 +361,47 @@ int phantom_conv2d_apply(const phantom_context *ctx, const phantom_conv_plan *pl
                          const uint64_t *const *const *key_digits, size_t dnum, const uint32_t *galois_elts,
                          uint64_t *const *outs, hipStream_t stream);
 
+/* ---- hoisted average pooling + fully connected layer (DNN::AvgPoolFullCon, src/dnn.cu:397-452) ----
+ * The reference pools each of the t input channels by 2 log2(width) sequential EvalRotateFused +
+ * EvalAddAuto steps, then forms T t constant products and additions, then adds the bias.  Pooling and
+ * the fully connected layer commute: here the channels are mixed first (t -> T, no key switch) and only
+ * T ciphertexts are pooled, each raised once per direction, the width - 1 rotations of a direction
+ * formed from the shared digits and summed in the Ext basis in one launch, then one moddown. */
+/* linear combinations with per-limb scalars, any K >= 1 and M >= 1 (phantom_leaf_combine stops at
+ * 16 x 8): outs[m] = sum_{k<K} ins[k] coef[m][k] + (cadd[m], 0) for m < M; ins / outs host arrays of
+ * device pointers to [2][Ql][n] ciphertexts (no output may alias an input), coef host [M][K][Ql]
+ * residues, cadd host [M][Ql] or NULL.  The 128-bit sums are reduced every 32 terms, so the result is
+ * the exact residue for every K: phantom_mul_scalar + modular additions term by term, bit for bit.
+ * Every input is read once per tile of up to 16 outputs (ceil(M / 16) times). */
+int phantom_ct_mix(const phantom_context *ctx, size_t chain_index, const uint64_t *const *ins, size_t K,
+                   const uint64_t *coef, const uint64_t *cadd, uint64_t *const *outs, size_t M, hipStream_t stream);
+/* hoisted rotate-and-sum in ONE launch: out [2][Ql+P][n] = the modular sum over k < count (1..63) of
+ * what phantom_fast_rotation_ext_batch writes for (key_digits[k], galois_elts[k]) with add_first = 1,
+ * plus phantom_keyswitch_ext(ct) when identity != 0, bit for bit; the count Ext ciphertexts are never
+ * written.  ct [2][Ql][n], digits [beta][Ql+P][n]; no key may be NULL; out must not alias ct / digits */
+int phantom_rotate_sum_ext(const phantom_context *ctx, size_t chain_index, const uint64_t *ct, const uint64_t *digits,
+                           const uint64_t *const *const *key_digits, size_t dnum, const uint32_t *galois_elts,
+                           size_t count, int identity, uint64_t *out, hipStream_t stream);
+/* the 2 (width - 1) pooling rotations, columns first: i 2^slotstr for i = 1..width-1, then
+ * j Lg 2^slotstr for j = 1..width-1 (Lg = width 2^slotstr).  Host only.  The reference
+ * (AddAvgPoolRotationsTo, src/dnn.cu:321-340) uses doubling steps and rotates rows by Lg 2^j, a row
+ * step only when slotstr = 0; these are the correct amounts for every slotstr. */
+int phantom_avgpool_rotations(size_t width, size_t slotstr, int *out, size_t capacity, size_t *count);
+/* the whole layer on raw ciphertexts: cts[k] [2][Ql][n] for k < t -> outs[u] [2][Ql][n] for u < T at the
+ * input's level.  In order: phantom_ct_mix (coef host [T][t][Ql], no cadd); per output phantom_modup
+ * of c1 and phantom_rotate_sum_ext over the width - 1 column rotations with the identity; the batched
+ * phantom_moddown_from_ntt of the 2 T polynomials; the same over the row rotations; cadd_bias (host
+ * [T][Ql] residues) added to c0.  col_keys[i] / row_keys[i]: host arrays of dnum device pointers for
+ * rotation i + 1 of the direction, col_elts / row_elts their Galois elements.  Enqueued on `stream`,
+ * scratch from the pool, not synchronised (a rotation key seen for the first time is uploaded as in
+ * phantom_keyswitch).  Refused with PHANTOM_ERR_INVALID_ARGUMENT before any launch: a null pointer,
+ * t or T of 0, width not a power of two in 2..64, ns = Lg^2 > N/2, a chain index of 0 or past the end,
+ * no special prime, a null key. */
+int phantom_avgpool_fc(const phantom_context *ctx, size_t chain_index, const uint64_t *const *cts, size_t t, size_t T,
+                       size_t width, size_t slotstr, const uint64_t *coef, const uint64_t *cadd_bias,
+                       const uint64_t *const *const *col_keys, const uint64_t *const *const *row_keys, size_t dnum,
+                       const uint32_t *col_elts, const uint32_t *row_elts, uint64_t *const *outs, hipStream_t stream);
+
 /* ---- serialization (host memory; no GPU involved) ------------------------------------
  * The byte format of PhantomCiphertext::save / load (include/ciphertext.h:184-225): the header
  * fields one by one (4 x size_t, double, uint64_t, size_t, bool, bool = 58 bytes) followed by

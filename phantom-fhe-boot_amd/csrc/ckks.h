@@ -102,6 +102,38 @@ struct LeafArgs {
 };
 hipError_t leaf_combine(const LeafArgs& a, size_t n, hipStream_t s);
 
+// ---- ct_mix: M linear combinations of K ciphertexts, K and M arbitrary (pool.hip) -------------
+//   out[m][p][l][e] = sum_{k < K} in[k][p][l][e] * c[m][k][l] + (p == 0 ? cadd[m][l] : 0)   (mod q_l)
+// in[k], out[m]: contiguous [2][L][n] ciphertexts, each list a device pointer table or (table null) a
+// base pointer with a stride in words (as MacArgs).  coef: device [L][K][m_pad] residues below q_l,
+// m_pad = mix_tiles(M) * mix_tile(M), the padding zero; cadd: device [M][L] or null.
+//
+// One thread owns one element of one limb for a tile of mix_tile(M) <= kMixTile outputs, whose
+// 128-bit sums stay in registers (no scratch); the coefficients are workgroup-uniform and come
+// through the scalar cache.  Every input is read once per tile: once for M <= kMixTile, else
+// mix_tiles(M) = ceil(M / kMixTile) times.  A product is below q^2, so with q < 2^61 a 128-bit sum
+// holds 64 products and the 65th can overflow (q < 2^60: 256 and the 257th): the sum is
+// Barrett-reduced to below q after every kMixBlock = 32 terms and carried on (at most
+// q + 32 q^2 < 2^128).  The result is the exact residue, hence bit-identical to mul_scalar and
+// add_mod term by term.
+constexpr int kMixTile = 16, kMixBlock = 32;
+constexpr size_t mix_tiles(size_t M) { return (M + kMixTile - 1) / kMixTile; }
+constexpr size_t mix_tile(size_t M) { return (M + mix_tiles(M) - 1) / mix_tiles(M); }
+struct MixArgs {
+  const uint64_t* const* ins = nullptr;  // device table [K], or
+  const uint64_t* in0 = nullptr;
+  uint64_t in_stride = 0;
+  uint64_t* const* outs = nullptr;  // device table [M], or
+  uint64_t* out0 = nullptr;
+  uint64_t out_stride = 0;
+  const uint64_t* coef = nullptr;
+  const uint64_t* cadd = nullptr;
+  const uint64_t* q = nullptr;
+  const uint64_t* barrett = nullptr;  // [L][2]
+  uint32_t K = 0, M = 0, L = 0;
+};
+hipError_t ct_mix(const MixArgs& a, size_t n, hipStream_t s);
+
 // out[l] = in[l] * c[l] (+ acc[l]) with per-limb constants passed by value (no device upload);
 // L <= kMaxScalarLimbs
 constexpr int kMaxScalarLimbs = 64;

@@ -251,6 +251,36 @@ struct KsRotateBatchGroupArgs {
 };
 hipError_t keyswitch_rotate_batch_group(const KsRotateBatchGroupArgs& ga, size_t n, hipStream_t s);
 
+// Hoisted rotate-and-sum: the modular sum of `count` (1..kKsSumMax) keyswitch_rotate results (mode 1)
+// of one ciphertext, plus P (c0, c1) when `identity`, in ONE launch and with one write of out:
+//   v_k[t][l][j] = sum_b digits[b][l][j] * evk_k[b][t][row(l)][j]  (+ P c0[l][j] for t = 0, l < Ql)
+//   out[t][l][i] = (identity && l < Ql ? P ct[t][l][i] : 0) + sum_k v_k[t][l][perm_k[i]]   (mod q_l)
+// A workgroup owns an OUTPUT block (limb l, min(n, kGaloisBlock) indices): for each entry it forms
+// the inner product of that entry's source block (perm_k[block start] & ~(bsz - 1)) into a
+// double-buffered LDS tile and gathers it into running sums held in registers, so the `count`
+// extended-basis ciphertexts that keyswitch_rotate_batch + poly_add_many would write and read back
+// never exist.  Per entry a workgroup reads its keys (2 beta words per element) and the digits of
+// the source block (beta words per element).  Bit-identical to that composition.
+constexpr uint32_t kKsSumMax = 63;
+struct KsSumEntry {
+  const uint64_t* const* evk = nullptr;  // device array of beta key pointers
+  const uint32_t* perm = nullptr;        // NTT-domain permutation of the rotation
+};
+struct KsRotateSumArgs {
+  const uint64_t* digits = nullptr;      // [beta][QlP][n]
+  const KsSumEntry* entries = nullptr;   // device array of `count` entries
+  uint32_t count = 0;
+  uint32_t identity = 0;
+  const uint64_t* qp = nullptr;          // full-chain modulus / Barrett tables (by table row)
+  const uint64_t* qp_barrett = nullptr;
+  const uint64_t* ct = nullptr;          // [2][Ql][n]
+  const uint64_t* pmod = nullptr;        // P mod q_l, Shoup
+  const uint64_t* pmod_shoup = nullptr;
+  uint64_t* out = nullptr;               // [2][QlP][n]; must not alias digits / ct
+  uint32_t ql = 0, qlp = 0, size_q = 0, size_p = 0, beta = 0;
+};
+hipError_t keyswitch_rotate_sum(const KsRotateSumArgs& a, size_t n, hipStream_t s);
+
 struct GaloisFinishArgs {
   const uint64_t* cx;
   const uint64_t* c0;

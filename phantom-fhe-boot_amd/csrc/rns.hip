@@ -1056,6 +1056,213 @@ __global__ __launch_bounds__(kBlock) void ks_rotate_batch_kernel(KsRotateBatchAr
   }
 }
 
+// keyswitch_rotate_sum: workgroup = (limb l, OUTPUT block ob).  Entry k's source block differs from
+// entry to entry, so its digits and c0 are loaded with its keys; the products go to LDS buffer k & 1
+// (one barrier per entry, as ks_rotate_batch_full) and are gathered into per-thread running sums
+// that stay in registers until the single write of out.
+//
+// Full blocks (BETA 1..4): the split partial sums and the exact reduction of ks_rotate_batch_full
+// (ll, hh <= 4 (2^31 - 1)^2 and mm <= 8 (2^30 - 1)(2^31 - 1), all below 2^64, for moduli up to 61
+// bits).  Entry k + 1's keys, digits and c0 are issued before entry k's barrier and gather.  The c0
+// words are loaded on every limb (limb 0's on the special limbs, times a zero constant) so that no
+// branch stands between the loads and the barrier.
+template <int BETA>
+// (BETA = 3 needs 12 bytes of scratch at the 128 registers of 4 waves per SIMD; it takes 3, as BETA = 4)
+__global__ __launch_bounds__(kBlock, BETA <= 2 ? 4 : 3) void ks_rotate_sum_full(KsRotateSumArgs a, uint32_t log_n) {
+  constexpr uint32_t bsz = kGalB;
+  constexpr int PP = kGalB / 2 / kBlock;  // pairs per thread
+  constexpr int GM = bsz / kBlock;        // gathered outputs per thread
+  static_assert(BETA <= 4, "split partial sums");
+  constexpr uint64_t kM30 = (1ull << 30) - 1;
+  __shared__ uint64_t s0[2][kGalB], s1[2][kGalB];
+  __shared__ const uint64_t* kp[kKsSumMax][BETA];
+  __shared__ const uint32_t* pp[kKsSumMax];  // the entry's permutation at this output block
+  __shared__ uint32_t sbk[kKsSumMax];        // the entry's source block (first index)
+  const uint32_t nb = (1u << log_n) / bsz;
+  const uint32_t l = blockIdx.x / nb, ob = blockIdx.x % nb;
+  const uint32_t twr = l >= a.ql ? a.size_q + (l - a.ql) : l;
+  const uint64_t q = a.qp[twr], r0 = a.qp_barrett[2 * twr], r1 = a.qp_barrett[2 * twr + 1];
+  const size_t lbase = (size_t)l << log_n, kbase = (size_t)twr << log_n;
+  const size_t qlp_n = (size_t)a.qlp << log_n, ql_n = (size_t)a.ql << log_n;
+  const size_t qp_n = (size_t)(a.size_q + a.size_p) << log_n;
+  const bool addc = l < a.ql;
+  const uint64_t w = addc ? a.pmod[l] : 0, ws = addc ? a.pmod_shoup[l] : 0;
+  const size_t cbase = addc ? lbase : 0;  // c0 words read on a special limb are multiplied by w = 0
+  const SplitRed sr = split_red(q, r0, r1);
+  if (threadIdx.x < a.count) {
+    const KsSumEntry en = a.entries[threadIdx.x];
+    const uint32_t* pm = en.perm + (size_t)ob * bsz;
+    pp[threadIdx.x] = pm;
+    sbk[threadIdx.x] = pm[0] & ~(bsz - 1);
+#pragma unroll
+    for (int b = 0; b < BETA; ++b) kp[threadIdx.x][b] = en.evk[b];
+  }
+  uint64_t acc0[GM], acc1[GM];
+#pragma unroll
+  for (int m = 0; m < GM; ++m) {
+    acc0[m] = 0;
+    acc1[m] = 0;
+    if (a.identity && addc) {  // workgroup-uniform; nothing in flight yet
+      const size_t e = lbase + (size_t)ob * bsz + threadIdx.x + m * kBlock;
+      acc0[m] = mul_shoup(a.ct[e], w, ws, q);
+      acc1[m] = mul_shoup(a.ct[ql_n + e], w, ws, q);
+    }
+  }
+  __syncthreads();
+  const int nk = static_cast<int>(a.count);
+  u64x2 dg[PP][BETA], k0[PP][BETA], k1[PP][BETA], c0[PP];
+  auto load_entry = [&](int k) {
+    const size_t j0 = __builtin_amdgcn_readfirstlane(sbk[k]);
+#pragma unroll
+    for (int b = 0; b < BETA; ++b) {
+      const uint64_t* key = uniform_ptr(kp[k][b]);
+#pragma unroll
+      for (int p = 0; p < PP; ++p) {
+        const size_t j = j0 + 2 * (threadIdx.x + p * kBlock);
+        k0[p][b] = ld2_nt(key + kbase + j);  // the keys are read once
+        k1[p][b] = ld2_nt(key + qp_n + kbase + j);
+        dg[p][b] = ld2(a.digits + b * qlp_n + lbase + j);
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < PP; ++p) c0[p] = ld2(a.ct + cbase + j0 + 2 * (threadIdx.x + p * kBlock));
+  };
+  load_entry(0);
+  for (int k = 0; k < nk; ++k) {
+    uint64_t* t0 = s0[k & 1];
+    uint64_t* t1 = s1[k & 1];
+    // the gather's permutation first: loads are waited for in issue order, so one issued after
+    // the next entry's operands would make the gather wait for those too
+    const __attribute__((address_space(1))) uint32_t* pm =
+        (const __attribute__((address_space(1))) uint32_t*)uniform_ptr(pp[k]);
+    uint32_t src[GM];
+#pragma unroll
+    for (int m = 0; m < GM; ++m) src[m] = pm[threadIdx.x + m * kBlock];
+    asm volatile("" ::: "memory");  // (issued here, not sunk to their use after the operand loads)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < PP; ++p) {
+      const uint32_t i = threadIdx.x + p * kBlock;
+      uint64_t ll[2][2] = {{0, 0}, {0, 0}}, mm[2][2] = {{0, 0}, {0, 0}}, hh[2][2] = {{0, 0}, {0, 0}};
+#pragma unroll
+      for (int b = 0; b < BETA; ++b) {
+        const uint64_t dv[2] = {dg[p][b].x, dg[p][b].y};
+        const uint64_t kv[2][2] = {{k0[p][b].x, k0[p][b].y}, {k1[p][b].x, k1[p][b].y}};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const uint32_t dl = static_cast<uint32_t>(dv[u] & kM30), dh = static_cast<uint32_t>(dv[u] >> 30);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const uint32_t kl = static_cast<uint32_t>(kv[t][u] & kM30), kh = static_cast<uint32_t>(kv[t][u] >> 30);
+            ll[t][u] += static_cast<uint64_t>(dl) * kl;
+            mm[t][u] += static_cast<uint64_t>(dl) * kh;
+            mm[t][u] += static_cast<uint64_t>(dh) * kl;
+            hh[t][u] += static_cast<uint64_t>(dh) * kh;
+          }
+        }
+      }
+      t0[2 * i] = add_mod(split_reduce_exact(ll[0][0], mm[0][0], hh[0][0], sr, q, r1), mul_shoup(c0[p].x, w, ws, q), q);
+      t0[2 * i + 1] = add_mod(split_reduce_exact(ll[0][1], mm[0][1], hh[0][1], sr, q, r1), mul_shoup(c0[p].y, w, ws, q), q);
+      t1[2 * i] = split_reduce_exact(ll[1][0], mm[1][0], hh[1][0], sr, q, r1);
+      t1[2 * i + 1] = split_reduce_exact(ll[1][1], mm[1][1], hh[1][1], sr, q, r1);
+    }
+    // the next entry's operands (the last one's again at the end: L2 hits) in flight over the
+    // barrier and the gather
+    __builtin_amdgcn_sched_barrier(0);
+    load_entry(min(k + 1, nk - 1));
+    ks_lt_barrier();
+#pragma unroll
+    for (int m = 0; m < GM; ++m) {
+      acc0[m] = add_mod(acc0[m], t0[src[m] & (bsz - 1)], q);
+      acc1[m] = add_mod(acc1[m], t1[src[m] & (bsz - 1)], q);
+    }
+  }
+  uint64_t* out = a.out + lbase + (size_t)ob * bsz;
+#pragma unroll
+  for (int m = 0; m < GM; ++m) {
+    out[threadIdx.x + m * kBlock] = acc0[m];
+    out[qlp_n + threadIdx.x + m * kBlock] = acc1[m];
+  }
+}
+
+// any block size / beta: 128-bit sums and a Barrett reduction per entry, the running sums in registers
+__global__ __launch_bounds__(kBlock) void ks_rotate_sum_kernel(KsRotateSumArgs a, uint32_t log_n, uint32_t bsz) {
+  constexpr int GM = kGalB / kBlock;
+  __shared__ uint64_t s0[2][kGalB], s1[2][kGalB];
+  const uint32_t nb = (1u << log_n) / bsz;
+  const uint32_t l = blockIdx.x / nb, ob = blockIdx.x % nb;
+  const uint32_t twr = l >= a.ql ? a.size_q + (l - a.ql) : l;
+  const uint64_t q = a.qp[twr], r0 = a.qp_barrett[2 * twr], r1 = a.qp_barrett[2 * twr + 1];
+  const size_t lbase = (size_t)l << log_n, kbase = (size_t)twr << log_n;
+  const size_t qlp_n = (size_t)a.qlp << log_n, ql_n = (size_t)a.ql << log_n;
+  const size_t qp_n = (size_t)(a.size_q + a.size_p) << log_n;
+  const bool addc = l < a.ql;
+  const uint64_t w = addc ? a.pmod[l] : 0, ws = addc ? a.pmod_shoup[l] : 0;
+  uint64_t acc0[GM], acc1[GM];
+#pragma unroll
+  for (int m = 0; m < GM; ++m) {
+    const uint32_t i = threadIdx.x + m * kBlock;
+    acc0[m] = 0;
+    acc1[m] = 0;
+    if (a.identity && addc && i < bsz) {
+      const size_t e = lbase + (size_t)ob * bsz + i;
+      acc0[m] = mul_shoup(a.ct[e], w, ws, q);
+      acc1[m] = mul_shoup(a.ct[ql_n + e], w, ws, q);
+    }
+  }
+  for (uint32_t k = 0; k < a.count; ++k) {
+    const KsSumEntry e = a.entries[k];
+    const uint32_t* pm = e.perm + (size_t)ob * bsz;
+    const size_t j0 = pm[0] & ~(bsz - 1);
+    uint64_t* t0 = s0[k & 1];
+    uint64_t* t1 = s1[k & 1];
+    for (uint32_t i = threadIdx.x; i < bsz / 2; i += kBlock) {
+      const size_t j = j0 + 2 * i;
+      u128 a0x{0, 0}, a0y{0, 0}, a1x{0, 0}, a1y{0, 0};
+      for (uint32_t b = 0; b < a.beta; ++b) {
+        const u64x2 c = ld2(a.digits + b * qlp_n + lbase + j);
+        const uint64_t* key = e.evk[b];
+        const u64x2 k0 = ld2(key + kbase + j), k1 = ld2(key + qp_n + kbase + j);
+        add128(a0x, mul_wide(c.x, k0.x));
+        add128(a0y, mul_wide(c.y, k0.y));
+        add128(a1x, mul_wide(c.x, k1.x));
+        add128(a1y, mul_wide(c.y, k1.y));
+      }
+      uint64_t v0x = barrett_reduce_128(a0x, q, r0, r1), v0y = barrett_reduce_128(a0y, q, r0, r1);
+      if (addc) {
+        const u64x2 c0 = ld2(a.ct + lbase + j);
+        v0x = add_mod(v0x, mul_shoup(c0.x, w, ws, q), q);
+        v0y = add_mod(v0y, mul_shoup(c0.y, w, ws, q), q);
+      }
+      t0[2 * i] = v0x;
+      t0[2 * i + 1] = v0y;
+      t1[2 * i] = barrett_reduce_128(a1x, q, r0, r1);
+      t1[2 * i + 1] = barrett_reduce_128(a1y, q, r0, r1);
+    }
+    // one barrier per entry: entry k's gather ends before any thread passes entry k + 1's barrier,
+    // so entry k + 2 may overwrite buffer k & 1
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < GM; ++m) {
+      const uint32_t i = threadIdx.x + m * kBlock;
+      if (i < bsz) {
+        const uint32_t src = pm[i] & (bsz - 1);
+        acc0[m] = add_mod(acc0[m], t0[src], q);
+        acc1[m] = add_mod(acc1[m], t1[src], q);
+      }
+    }
+  }
+  uint64_t* out = a.out + lbase + (size_t)ob * bsz;
+#pragma unroll
+  for (int m = 0; m < GM; ++m) {
+    const uint32_t i = threadIdx.x + m * kBlock;
+    if (i < bsz) {
+      out[i] = acc0[m];
+      out[qlp_n + i] = acc1[m];
+    }
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void galois_kernel(const uint64_t* __restrict__ in, uint64_t* out,
                                                         const uint32_t* __restrict__ perm, uint32_t log_n,
                                                         uint32_t bsz) {
@@ -1381,6 +1588,22 @@ hipError_t keyswitch_rotate_batch(const KsRotateBatchArgs& a, size_t n, hipStrea
     case 3: ks_rotate_batch_full<3, false><<<grid, kBlock, 0, s>>>(KsRotateBatchGroupArgs{{a}, 1}, log_n); break;
     case 4: ks_rotate_batch_full<4, false><<<grid, kBlock, 0, s>>>(KsRotateBatchGroupArgs{{a}, 1}, log_n); break;
     default: ks_rotate_batch_kernel<<<grid, kBlock, 0, s>>>(a, log_n, bsz); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t keyswitch_rotate_sum(const KsRotateSumArgs& a, size_t n, hipStream_t s) {
+  if (!a.digits || !a.entries || !a.ct || !a.out || !a.pmod || !a.pmod_shoup || a.beta == 0 || a.ql == 0 ||
+      a.ql > a.qlp || a.count < 1 || a.count > kKsSumMax || n < 2 || (n & (n - 1)))
+    return hipErrorInvalidValue;
+  const uint32_t log_n = __builtin_ctzll(n), bsz = static_cast<uint32_t>(std::min<size_t>(n, kGalB));
+  const dim3 grid(static_cast<uint32_t>(a.qlp * (n / bsz)));
+  switch (bsz == kGalB ? a.beta : 0) {
+    case 1: ks_rotate_sum_full<1><<<grid, kBlock, 0, s>>>(a, log_n); break;
+    case 2: ks_rotate_sum_full<2><<<grid, kBlock, 0, s>>>(a, log_n); break;
+    case 3: ks_rotate_sum_full<3><<<grid, kBlock, 0, s>>>(a, log_n); break;
+    case 4: ks_rotate_sum_full<4><<<grid, kBlock, 0, s>>>(a, log_n); break;
+    default: ks_rotate_sum_kernel<<<grid, kBlock, 0, s>>>(a, log_n, bsz); break;
   }
   return hipGetLastError();
 }

@@ -7,6 +7,7 @@
 #include <string>
 #include <unordered_set>
 
+#include "avgpool.h"
 #include "buffer.h"
 #include "conv2d.h"
 #include "hip_check.h"
@@ -252,6 +253,107 @@ TensorCT DNN::Add(const TensorCT& a, const TensorCT& b) {
   result.ctks_.resize(a.num_ch_);
   for (size_t u = 0; u < a.num_ch_; ++u)
     result.ctks_[u] = EvalAddAuto(context_, a.ctks_[u], b.ctks_[u], m_scalingFactorsReal_, m_scalingFactorsRealBig_);
+  return result;
+}
+
+void DNN::AddAvgPoolRotationsTo(std::vector<int32_t>& rotation_indices, size_t input_width, size_t slotstr) {
+  avgpool_shape(context_.poly_degree(), input_width, slotstr);
+  std::unordered_set<int32_t> existing(rotation_indices.begin(), rotation_indices.end());
+  for (int r : avgpool_rotations(input_width, slotstr))
+    if (existing.insert(r).second) rotation_indices.push_back(r);
+}
+
+std::vector<uint64_t> DNN::mix_setup(const TensorCT& input, const std::vector<std::vector<double>>& weight,
+                                     const char* who, std::vector<PhantomCiphertext>& rescaled, TensorCT& result) {
+  const std::string name(who);
+  const size_t t = input.num_ch_, T = weight.size();
+  if (t == 0 || input.ctks_.size() != t) throw std::invalid_argument(name + ": channel count mismatch");
+  if (T == 0) throw std::invalid_argument(name + ": weight must be [T][t]");
+  for (const std::vector<double>& row : weight)
+    if (row.size() != t) throw std::invalid_argument(name + ": ragged weight, or its columns differ from the tensor's channels");
+  const PhantomCiphertext& first = input.ctks_[0];
+  for (const PhantomCiphertext& c : input.ctks_)
+    if (c.size() != 2 || c.chain_index() != first.chain_index() || c.scale() != first.scale() ||
+        c.GetNoiseScaleDeg() != first.GetNoiseScaleDeg())
+      throw std::invalid_argument(name + ": the channels must share level, noise-scale degree and scale");
+  // a degree-2 input is rescaled first (EvalMultConstInplace, include/evaluate.cuh:317-326)
+  if (first.GetNoiseScaleDeg() == 2) {
+    rescaled = input.ctks_;
+    for (PhantomCiphertext& c : rescaled) EvalModReduceInPlace(context_, c, 1);
+  }
+  const PhantomCiphertext& in0 = rescaled.empty() ? first : rescaled[0];
+  const size_t chain = in0.chain_index(), L = in0.coeff_modulus_size();
+  std::vector<uint64_t> coef(T * t * L);
+  for (size_t u = 0; u < T; ++u)
+    for (size_t k = 0; k < t; ++k) {
+      const std::vector<uint64_t> r = GetElementForEvalMult(context_, in0, weight[u][k], m_scalingFactorsReal_);
+      std::copy(r.begin(), r.begin() + L, coef.begin() + (u * t + k) * L);
+    }
+  result.width_ = input.width_;
+  result.slotstr_ = input.slotstr_;
+  result.num_ch_ = T;
+  result.ctks_.resize(T);
+  for (PhantomCiphertext& o : result.ctks_) {
+    o.resize(context_, chain, 2, context_.stream(), false);
+    o.set_ntt_form(true);
+    o.set_scale(in0.scale() * m_scalingFactorsReal_.at(level_of(in0)));  // EvalMultConstInplaceCore
+    o.SetNoiseScaleDeg(in0.GetNoiseScaleDeg() + 1);
+    o.set_correction_factor(in0.correction_factor());
+    o.set_asymmetric(in0.is_asymmetric());
+  }
+  return coef;
+}
+
+TensorCT DNN::MixChannels(const TensorCT& input, const std::vector<std::vector<double>>& weight) {
+  std::vector<PhantomCiphertext> rescaled;
+  TensorCT result;
+  const std::vector<uint64_t> coef = mix_setup(input, weight, "MixChannels", rescaled, result);
+  const std::vector<PhantomCiphertext>& in = rescaled.empty() ? input.ctks_ : rescaled;
+  const size_t t = in.size(), T = result.num_ch_, chain = in[0].chain_index();
+  std::vector<const uint64_t*> cts(t);
+  std::vector<uint64_t*> outs(T);
+  for (size_t k = 0; k < t; ++k) cts[k] = in[k].data();
+  for (size_t u = 0; u < T; ++u) outs[u] = result.ctks_[u].data();
+  hipStream_t s = context_.stream();
+  DeviceBuffer<uint64_t> table(mix_table_words(t, T, in[0].coeff_modulus_size()), s);
+  ct_mix_raw(context_, chain, cts.data(), t, coef.data(), nullptr, outs.data(), T, table.get(), s);
+  return result;
+}
+
+TensorCT DNN::AvgPoolFullCon(const TensorCT& input, const std::vector<std::vector<double>>& weight,
+                             const std::vector<double>& bias) {
+  if (bias.size() != weight.size()) throw std::invalid_argument("AvgPoolFullCon: one bias per weight row");
+  const size_t n = context_.poly_degree(), width = input.width_;
+  avgpool_shape(n, width, input.slotstr_);
+  const std::vector<int> rots = avgpool_rotations(width, input.slotstr_);
+  std::vector<const uint64_t* const*> evk(rots.size());
+  std::vector<uint32_t> elts(rots.size());
+  for (size_t i = 0; i < rots.size(); ++i) {
+    elts[i] = FindAutomorphismIndex2nComplex(rots[i], n);
+    if (!gk_.has(elts[i])) throw std::invalid_argument("AvgPoolFullCon: no rotation key for a step (AddAvgPoolRotationsTo)");
+    evk[i] = gk_.get(elts[i]).public_keys_ptr();
+  }
+  std::vector<PhantomCiphertext> rescaled;
+  TensorCT result;
+  const std::vector<uint64_t> coef = mix_setup(input, weight, "AvgPoolFullCon", rescaled, result);
+  const std::vector<PhantomCiphertext>& in = rescaled.empty() ? input.ctks_ : rescaled;
+  const size_t t = in.size(), T = result.num_ch_, chain = in[0].chain_index(), L = in[0].coeff_modulus_size();
+  // the bias residues of EvalAddConstInPlaceWrap at the output's level, degree and scale
+  const auto& mods = context_.get_context_data(chain).moduli();
+  std::vector<uint64_t> bres(T * L, 0);
+  for (size_t u = 0; u < T; ++u) {
+    if (bias[u] == 0) continue;
+    const std::vector<uint64_t> r = GetElementForEvalAddOrSub(context_, result.ctks_[u], std::fabs(bias[u]),
+                                                              m_scalingFactorsReal_, m_scalingFactorsRealBig_);
+    for (size_t l = 0; l < L; ++l) bres[u * L + l] = bias[u] > 0 ? r[l] : (r[l] ? mods[l] - r[l] : 0);
+  }
+  std::vector<const uint64_t*> cts(t);
+  std::vector<uint64_t*> outs(T);
+  for (size_t k = 0; k < t; ++k) cts[k] = in[k].data();
+  for (size_t u = 0; u < T; ++u) outs[u] = result.ctks_[u].data();
+  const size_t R = width - 1;
+  avgpool_fc_raw(context_, chain, cts.data(), t, T, width, input.slotstr_, coef.data(), bres.data(), evk.data(),
+                 evk.data() + R, elts.data(), elts.data() + R, outs.data(), context_.stream());
   return result;
 }
 

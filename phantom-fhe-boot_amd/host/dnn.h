@@ -2,10 +2,14 @@
 // engine: TensorCT and the DNN members that encrypt a tensor, convolve it, and chain two
 // convolutions (BatchNorm, Add).  Conv is the hoisted layer of host/conv2d.h instead of the
 // reference's out_ch in_ch K^2 rotate / multiply / add steps (src/dnn.cu:82-150); EncTensor and
-// DecTensor are one batched device call each.
+// DecTensor are one batched device call each.  AvgPoolFullCon is the hoisted layer of
+// host/avgpool.h: the channels are mixed first and only the T outputs are pooled, where the reference
+// pools every input channel by sequential key switches (src/dnn.cu:397-452).  Its row rotations are
+// j width 4^slotstr slots, a whole row; the reference's width 2^slotstr 2^j (src/dnn.cu:334-338,
+// :421) is a row step only for slotstr = 0, where both agree.
 //
-// Not built here: Relu, ReluDegTwo, Sign, ReluComposite, SoftMax, AvgPoolFullCon,
-// BootStrap, the weight loader and the ResNet driver.
+// Not built here: Relu, ReluDegTwo, Sign, ReluComposite, SoftMax, BootStrap, the
+// weight loader and the ResNet driver.
 #pragma once
 
 #include <cstdint>
@@ -115,12 +119,35 @@ class DNN {
   // channel-wise EvalAddAuto (src/dnn.cu:482-501)
   TensorCT Add(const TensorCT& a, const TensorCT& b);
 
+  // appends the 2 (width - 1) pooling rotations that the list lacks (avgpool_rotations: every column
+  // and row step, not the reference's doubling steps, src/dnn.cu:321-340)
+  void AddAvgPoolRotationsTo(std::vector<int32_t>& rotation_indices, size_t input_width, size_t slotstr);
+  // weight[u][k], u < T, k < t = num_ch_ (src/dnn.cu:397-452): out_u = sum_k weight[u][k] pool(in_k) +
+  // bias[u] in every pixel's slot the pooling reaches (pixel (0, 0) holds the full sum); the 1 / width^2
+  // of an average is the caller's to fold into the weights, as in the reference.  The coefficients
+  // are GetElementForEvalMult's and the bias residues EvalAddConstInPlaceWrap's at the output's scale.
+  // The result is at the input's level with noise-scale degree input + 1 and scale
+  // ct.scale * sf[level]; a degree-2 input is rescaled first, as EvalMultConstInplace does; width_
+  // and slotstr_ stay, num_ch_ = T.  std::invalid_argument: ragged or mismatched weights, channels at
+  // different levels, degrees or scales, a missing rotation key.
+  TensorCT AvgPoolFullCon(const TensorCT& input, const std::vector<std::vector<double>>& weight,
+                          const std::vector<double>& bias);
+  // the layer's first stage alone, out_u = sum_k weight[u][k] in_k in one launch (phx::ct_mix): equal
+  // to the EvalMultConst / EvalAddAuto loop word for word, with the metadata rules above
+  TensorCT MixChannels(const TensorCT& input, const std::vector<std::vector<double>>& weight);
+
  private:
   // the layer on dev_W (conv2d_raw), or on `plan` when it is not null (conv2d_apply)
   TensorCT conv_run(const TensorCT& input, const double* dev_W, const ConvPlanData* plan, size_t kernel_h, size_t out_ch,
                     size_t stride);
   static std::vector<double> flatten_weight(const Weight4& weight, size_t& K, size_t& in_ch, size_t& out_ch,
                                             const char* who);
+  // the checks, the rescale of a degree-2 input and the coefficient residues [T][t][L] that
+  // AvgPoolFullCon and MixChannels share; `rescaled` holds the channels to read when the input was
+  // of degree 2 (else it stays empty and the input's are read), `result` the outputs with their
+  // metadata set
+  std::vector<uint64_t> mix_setup(const TensorCT& input, const std::vector<std::vector<double>>& weight, const char* who,
+                                  std::vector<PhantomCiphertext>& rescaled, TensorCT& result);
 
   size_t scale_;
   PhantomGaloisKeyFused gk_;

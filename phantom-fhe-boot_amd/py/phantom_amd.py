@@ -135,6 +135,14 @@ _SIGS = {
     "phantom_encrypt_asymmetric_batch_chunk": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
     "phantom_boot_encrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp, sz, ctypes.POINTER(sz)]),
     "phantom_boot_decrypt_device": (ctypes.c_int, [vp, vp, sz, sz, vp]),
+    "phantom_ct_mix": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, vp, vp, ctypes.POINTER(vp), sz, vp]),
+    "phantom_rotate_sum_ext": (ctypes.c_int, [vp, sz, vp, vp, ctypes.POINTER(ctypes.POINTER(vp)), sz,
+                                              ctypes.POINTER(ctypes.c_uint32), sz, ctypes.c_int, vp, vp]),
+    "phantom_avgpool_rotations": (ctypes.c_int, [sz, sz, vp, sz, ctypes.POINTER(sz)]),
+    "phantom_avgpool_fc": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, sz, sz, sz, vp, vp,
+                                          ctypes.POINTER(ctypes.POINTER(vp)), ctypes.POINTER(ctypes.POINTER(vp)), sz,
+                                          ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                          ctypes.POINTER(vp), vp]),
     "phantom_conv_rotations": (ctypes.c_int, [sz, sz, sz, vp, sz, ctypes.POINTER(sz)]),
     "phantom_conv_weight_slots": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp, vp]),
     "phantom_conv_weight_slots_host": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp]),
