@@ -708,6 +708,32 @@ int phantom_encrypt_asymmetric_batch(const phantom_context *ctx, size_t chain_in
 /* host only: ciphertexts per internal chunk at this chain index */
 int phantom_encrypt_asymmetric_batch_chunk(const phantom_context *ctx, size_t chain_index, size_t *chunk);
 
+/* ---- channel packing for the tensor bootstrap (host/pack.h) -------------------------------------
+ * A sparse-packed channel of ns = (width 2^slotstr)^2 slots is a polynomial in X^(N / (2 ns)), so
+ * pack <= min(N / (2 ns), 64) channels (a power of two) are interleaved into one ciphertext by
+ * monomial shifts, packed = sum_c X^(c D) ct_c with D = N / (2 pack ns); one bootstrap at pack ns
+ * slots refreshes them all and a binary tree of rotations takes them apart: level t rotates every
+ * node a by rotations[t] = pack ns / 2^(t+1) slots and forms a + rot and (a - rot) X^(2N - powers[t]),
+ * powers[t] = D 2^t.  Ciphertexts are [2][L][N] words, NTT form, 16-byte aligned.  Bad arguments
+ * (a null pointer, C or count of 0 or above 64, a power >= 2N, a chain index of 0 or past the end, a
+ * misaligned ciphertext, an output overlapping an input other than even[k] == a[k]) return
+ * PHANTOM_ERR_INVALID_ARGUMENT before any launch. */
+/* host only: the log2(pack) tree levels for ring degree 2^log_n: rotations (slots), their Galois
+ * elements 5^r mod 2N and the shifts D 2^t the odd children undo (each array may be null); *count is set
+ * even when capacity is too small.  Refused: a width that is no power of two, a pack that is no
+ * power of two or above min(N / (2 ns), 64), an image that does not fit N / 2 slots. */
+int phantom_pack_rotations(size_t width, size_t slotstr, size_t pack, size_t log_n, int *rotations,
+                           uint32_t *galois_elts, uint32_t *powers, size_t capacity, size_t *count);
+/* out = sum_{c < C} X^(c stride_power) ins[c] (ins: host array of C device pointers) in one launch
+ * that reads every input once */
+int phantom_ct_pack(const phantom_context *ctx, size_t chain_index, const uint64_t *const *ins, size_t C,
+                    uint32_t stride_power, uint64_t *out, hipStream_t stream);
+/* one tree level of `count` nodes in one launch: even[k] = a[k] + r[k], odd[k] = (a[k] - r[k]) X^(2N - power)
+ * (host arrays of device pointers; even[k] or odd[k] may be null, and one of the two arrays too) */
+int phantom_ct_split(const phantom_context *ctx, size_t chain_index, const uint64_t *const *a,
+                     const uint64_t *const *r, size_t count, uint32_t power, uint64_t *const *even,
+                     uint64_t *const *odd, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,43 @@ struct MixArgs {
 };
 hipError_t ct_mix(const MixArgs& a, size_t n, hipStream_t s);
 
+// ---- ct_pack / ct_split: channel packing by monomial shifts and its rotation tree (pack.hip) ------
+// Ciphertexts are contiguous [2][L][n], NTT form, 16-byte aligned; q / barrett are the chain's rows.
+//   ct_pack:  out[p][l][i] = sum_{c < C} in_c[p][l][i] w[l][i]^c   (mod q_l),  w = NTT(X^D) [L][n]
+// by Horner from the top channel down, so w is loaded once per element and every input read once
+// (C + 1 reads of 2 L n words, counting w as L n, and one write).  Every step is fully reduced.
+// The pointers travel in the argument block for C <= kPackInline, else in a device table [C].
+//   ct_split: for node k < count, even_k = a_k + r_k and odd_k = (a_k - r_k) m,  m = NTT of a monomial [L][n]
+// in one launch (a_k and r_k read once; 2 reads + m and up to 2 writes per node).  even_k or odd_k
+// may be null (a pruned child); even_k may alias a_k, no other output may alias an input.
+constexpr int kPackMax = 64, kPackInline = 16, kSplitMax = 64, kSplitInline = 8;
+struct PackArgs {
+  const uint64_t* in[kPackInline] = {};
+  const uint64_t* const* table = nullptr;  // device [C]: read instead of `in` when not null
+  const uint64_t* w = nullptr;
+  uint64_t* out = nullptr;
+  const uint64_t* q = nullptr;
+  const uint64_t* barrett = nullptr;  // [L][2]
+  uint32_t C = 0, L = 0;
+  uint32_t lead = 0;  // out = w^lead sum_c in_c w^c: channel 0 at index `lead` (C + lead <= kPackMax)
+};
+hipError_t ct_pack(const PackArgs& a, size_t n, hipStream_t s);
+struct SplitNode {
+  const uint64_t* a;
+  const uint64_t* r;
+  uint64_t* even;
+  uint64_t* odd;
+};
+struct SplitArgs {
+  SplitNode node[kSplitInline] = {};
+  const SplitNode* table = nullptr;  // device [count]: read instead of `node` when not null
+  const uint64_t* m = nullptr;
+  const uint64_t* q = nullptr;
+  const uint64_t* barrett = nullptr;  // [L][2]
+  uint32_t count = 0, L = 0;
+};
+hipError_t ct_split(const SplitArgs& a, size_t n, hipStream_t s);
+
 // out[l] = in[l] * c[l] (+ acc[l]) with per-limb constants passed by value (no device upload);
 // L <= kMaxScalarLimbs
 constexpr int kMaxScalarLimbs = 64;

@@ -1152,13 +1152,15 @@ static void trace(const PhantomContext& cc, const char* stage, const PhantomCiph
 
 std::vector<PhantomCiphertext> FHECKKSRNS::EvalBootstrapBatch(const std::vector<PhantomCiphertext>& in,
                                                               const PhantomContext& cc, int lanes,
-                                                              uint32_t numSlots, size_t group) const {
+                                                              uint32_t numSlots, size_t group,
+                                                              uint32_t post_shift) const {
   // a call from one of this function's own lane threads (a nested batch) runs serially on the
   // caller's lane: its lane streams are already in use by the outer batch
   static thread_local bool on_lane = false;
   const int k = on_lane ? 1 : std::max(1, std::min({lanes, PhantomContext::kLanes, static_cast<int>(in.size())}));
   if (group < 1 || group > static_cast<size_t>(phx::kLtGroupMax))
     throw std::invalid_argument("EvalBootstrapBatch: group must be 1.." + std::to_string(phx::kLtGroupMax));
+  closing_integer(post_shift);  // refused before any lane starts
   std::vector<PhantomCiphertext> out(in.size());
   // ciphertexts t, t + k, ... of lane t, up to `group` at a time in lockstep (shared plaintext
   // and key reads, EvalMod on 2 x group lanes).  A lane's m ciphertexts form ceil(m / group)
@@ -1174,12 +1176,12 @@ std::vector<PhantomCiphertext> FHECKKSRNS::EvalBootstrapBatch(const std::vector<
       const size_t at = g0;
       g0 += cnt;
       if (cnt == 1) {
-        out[mine[at]] = EvalBootstrap(in[mine[at]], cc, numSlots);
+        out[mine[at]] = EvalBootstrap(in[mine[at]], cc, numSlots, 1, 0, post_shift);
         continue;
       }
       std::vector<const PhantomCiphertext*> grp;
       for (size_t m = 0; m < cnt; ++m) grp.push_back(&in[mine[at + m]]);
-      std::vector<PhantomCiphertext> r = bootstrap_group(grp, cc, pc);
+      std::vector<PhantomCiphertext> r = bootstrap_group(grp, cc, pc, post_shift);
       for (size_t m = 0; m < cnt; ++m) out[mine[at + m]] = std::move(r[m]);
     }
   };
@@ -1227,9 +1229,12 @@ std::vector<PhantomCiphertext> FHECKKSRNS::EvalBootstrapBatch(const std::vector<
 }
 
 PhantomCiphertext FHECKKSRNS::EvalBootstrap(const PhantomCiphertext& in, const PhantomContext& cc, uint32_t numSlots,
-                                            uint32_t numIterations, uint32_t precision) const {
+                                            uint32_t numIterations, uint32_t precision, uint32_t post_shift) const {
+  const uint64_t closing = closing_integer(post_shift);
   const Precom& pc = precom(numSlots, cc);
-  if (numIterations <= 1) return bootstrap_once(in, cc, pc);
+  if (numIterations <= 1) return bootstrap_once(in, cc, pc, post_shift);
+  if (closing != uint64_t(1) << correction_)
+    throw std::invalid_argument("iterative bootstrapping takes no post_shift");
   // iterative bootstrapping (bootstrap.cu:856-900): the first bootstrap's error, scaled up by
   // 2^precision, is bootstrapped again and subtracted
   if (precision < 1 || precision > 30) throw std::invalid_argument("iterative bootstrapping needs a precision in [1, 30]");
@@ -1262,12 +1267,14 @@ PhantomCiphertext FHECKKSRNS::EvalBootstrap(const PhantomCiphertext& in, const P
 }
 
 std::vector<PhantomCiphertext> FHECKKSRNS::bootstrap_group(const std::vector<const PhantomCiphertext*>& in,
-                                                           const PhantomContext& cc, const Precom& pc) const {
+                                                           const PhantomContext& cc, const Precom& pc,
+                                                           uint32_t post_shift) const {
   const uint32_t N = static_cast<uint32_t>(cc.poly_degree()), M = 2 * N;
   const size_t K = in.size();
+  const uint64_t closing = closing_integer(post_shift);
   if (pc.slots != N / 2 || K < 2) {
     std::vector<PhantomCiphertext> r;
-    for (const PhantomCiphertext* c : in) r.push_back(bootstrap_once(*c, cc, pc));
+    for (const PhantomCiphertext* c : in) r.push_back(bootstrap_once(*c, cc, pc, post_shift));
     return r;
   }
   std::vector<PhantomCiphertext> x;
@@ -1298,12 +1305,20 @@ std::vector<PhantomCiphertext> FHECKKSRNS::bootstrap_group(const std::vector<con
     EvalAddAutoInplace(cc, x[c], im, sf_);
   }
   for (const LTLevel& lv : pc.dec) level(lv);
-  for (PhantomCiphertext& d : x) MultByIntegerInPlace(cc, d, uint64_t(1) << correction_);
+  for (PhantomCiphertext& d : x) MultByIntegerInPlace(cc, d, closing);
   return x;
 }
 
-PhantomCiphertext FHECKKSRNS::bootstrap_once(const PhantomCiphertext& in, const PhantomContext& cc,
-                                             const Precom& pc) const {
+uint64_t FHECKKSRNS::closing_integer(uint32_t post_shift) const {
+  if (post_shift > correction_)
+    throw std::invalid_argument("bootstrap: post_shift " + std::to_string(post_shift) + " exceeds the correction factor " +
+                                std::to_string(correction_));
+  return uint64_t(1) << (correction_ - post_shift);
+}
+
+PhantomCiphertext FHECKKSRNS::bootstrap_once(const PhantomCiphertext& in, const PhantomContext& cc, const Precom& pc,
+                                             uint32_t post_shift) const {
+  const uint64_t closing = closing_integer(post_shift);
   const uint32_t N = static_cast<uint32_t>(cc.poly_degree()), M = 2 * N;
   const uint32_t slots = pc.slots;
   trace(cc, "start", in);
@@ -1356,8 +1371,8 @@ PhantomCiphertext FHECKKSRNS::bootstrap_once(const PhantomCiphertext& in, const 
     add_inplace(cc, dec, r);
   }
   trace(cc, "stc", dec);
-  // undo the correction scaling
-  MultByIntegerInPlace(cc, dec, uint64_t(1) << correction_);
+  // undo the correction scaling (less the caller's post_shift)
+  MultByIntegerInPlace(cc, dec, closing);
   return dec;
 }
 

@@ -82,8 +82,13 @@ class FHECKKSRNS {
   // EvalBootstrap (bootstrap.cu:843-1129); the input needs at least two limbs.  numSlots: the
   // setup to use (0: N/2).  numIterations > 1: iterative bootstrapping (bootstrap.cu:856-900):
   // bootstrap, scale the residual error up by 2^precision, bootstrap it and subtract.
+  // post_shift = g closes the bootstrap with the integer 2^(correction - g) instead of
+  // 2^correction: the result is the message divided by 2^g at the canonical scale, at no cost in
+  // precision or levels (the signal inside the bootstrap is unchanged), for a caller that multiplies
+  // by 2^g afterwards (the channel tree of host/pack.h).  0 leaves every result as it was;
+  // std::invalid_argument for g > correction_factor() or with numIterations > 1.
   PhantomCiphertext EvalBootstrap(const PhantomCiphertext& ct, const PhantomContext& cc, uint32_t numSlots = 0,
-                                  uint32_t numIterations = 1, uint32_t precision = 0) const;
+                                  uint32_t numIterations = 1, uint32_t precision = 0, uint32_t post_shift = 0) const;
   // EvalBootstrapBatch's default lockstep group (a run-time choice: the group argument below,
   // phantom_boot_run_grouped at the C-ABI)
   static constexpr size_t kBootGroup = 8;
@@ -95,7 +100,7 @@ class FHECKKSRNS {
   // on cc.stream()
   std::vector<PhantomCiphertext> EvalBootstrapBatch(const std::vector<PhantomCiphertext>& in,
                                                     const PhantomContext& cc, int lanes, uint32_t numSlots = 0,
-                                                    size_t group = kBootGroup) const;
+                                                    size_t group = kBootGroup, uint32_t post_shift = 0) const;
 
   // stages, exposed for tests and the benchmark (full packing setup unless numSlots is given)
   PhantomCiphertext EvalCoeffsToSlots(const PhantomCiphertext& ct, const PhantomContext& cc,
@@ -284,11 +289,16 @@ class FHECKKSRNS {
   std::vector<PhantomCiphertext> chebyshev_lanes(std::vector<PhantomCiphertext> in, const PhantomContext& cc,
                                                  const std::vector<double>& coeffs) const;
   void double_angle_lanes(std::vector<PhantomCiphertext>& v, const PhantomContext& cc, uint32_t numIter) const;
-  PhantomCiphertext bootstrap_once(const PhantomCiphertext& ct, const PhantomContext& cc, const Precom& pc) const;
+  // post_shift: EvalBootstrap's
+  PhantomCiphertext bootstrap_once(const PhantomCiphertext& ct, const PhantomContext& cc, const Precom& pc,
+                                   uint32_t post_shift = 0) const;
   // bootstrap_once of 2..8 ciphertexts in lockstep (full packing): grouped linear-transform levels,
   // EvalMod on 2 x group lanes; each result equals bootstrap_once's, bit for bit
   std::vector<PhantomCiphertext> bootstrap_group(const std::vector<const PhantomCiphertext*>& in,
-                                                 const PhantomContext& cc, const Precom& pc) const;
+                                                 const PhantomContext& cc, const Precom& pc,
+                                                 uint32_t post_shift = 0) const;
+  // the closing integer 2^(correction_ - post_shift), or std::invalid_argument
+  uint64_t closing_integer(uint32_t post_shift) const;
 
   PhantomCKKSEncoder& encoder_;
   std::vector<double> sf_, sf_big_;

@@ -1,6 +1,7 @@
 // dnn.cpp — see dnn.h
 #include "dnn.h"
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <stdexcept>
@@ -11,6 +12,7 @@
 #include "buffer.h"
 #include "conv2d.h"
 #include "hip_check.h"
+#include "pack.h"
 
 namespace phantom {
 
@@ -355,6 +357,177 @@ TensorCT DNN::AvgPoolFullCon(const TensorCT& input, const std::vector<std::vecto
   avgpool_fc_raw(context_, chain, cts.data(), t, T, width, input.slotstr_, coef.data(), bres.data(), evk.data(),
                  evk.data() + R, elts.data(), elts.data() + R, outs.data(), context_.stream());
   return result;
+}
+
+void DNN::check_uniform(const TensorCT& input, const char* who) const {
+  const std::string name(who);
+  if (input.num_ch_ == 0 || input.ctks_.size() != input.num_ch_) throw std::invalid_argument(name + ": channel count mismatch");
+  const PhantomCiphertext& first = input.ctks_[0];
+  for (const PhantomCiphertext& c : input.ctks_)
+    if (c.size() != 2 || c.chain_index() != first.chain_index() || c.scale() != first.scale() ||
+        c.GetNoiseScaleDeg() != first.GetNoiseScaleDeg())
+      throw std::invalid_argument(name + ": the channels must share level, noise-scale degree and scale");
+}
+
+size_t DNN::PackCapacity(size_t width, size_t slotstr) const {
+  return pack_capacity(context_.poly_degree(), width, slotstr);
+}
+
+void DNN::AddPackRotationsTo(std::vector<int32_t>& rotation_indices, size_t input_width, size_t slotstr, size_t pack) {
+  const PackPlan plan = pack_plan(context_.poly_degree(), input_width, slotstr, pack);
+  std::unordered_set<int32_t> existing(rotation_indices.begin(), rotation_indices.end());
+  for (int r : plan.rotations)
+    if (existing.insert(r).second) rotation_indices.push_back(r);
+}
+
+PackedCT DNN::Pack(const TensorCT& input, size_t pack) {
+  const PackPlan plan = pack_plan(context_.poly_degree(), input.width_, input.slotstr_, pack);
+  check_uniform(input, "Pack");
+  PackedCT out;
+  out.width_ = input.width_;
+  out.slotstr_ = input.slotstr_;
+  out.num_ch_ = input.num_ch_;
+  out.pack_ = pack;
+  for (size_t grp = 0; grp < plan.groups(input.num_ch_); ++grp) {
+    std::vector<const PhantomCiphertext*> members(plan.members(input.num_ch_, grp));
+    for (size_t c = 0; c < members.size(); ++c) members[c] = &input.ctks_[grp * pack + c];
+    out.ctks_.push_back(pack_channels(context_, plan, members.data(), members.size()));
+  }
+  return out;
+}
+
+TensorCT DNN::Unpack(const PackedCT& packed) {
+  const PackPlan plan = pack_plan(context_.poly_degree(), packed.width_, packed.slotstr_, packed.pack_);
+  if (packed.num_ch_ == 0 || packed.ctks_.size() != plan.groups(packed.num_ch_))
+    throw std::invalid_argument("Unpack: group count mismatch");
+  for (const PhantomCiphertext& c : packed.ctks_)
+    if (c.size() != 2 || c.chain_index() != packed.ctks_[0].chain_index() || c.scale() != packed.ctks_[0].scale() ||
+        c.GetNoiseScaleDeg() != packed.ctks_[0].GetNoiseScaleDeg())
+      throw std::invalid_argument("Unpack: the groups must share level, noise-scale degree and scale");
+  for (uint32_t e : plan.galois)
+    if (!gk_.has(e)) throw std::invalid_argument("Unpack: no rotation key for a tree level (AddPackRotationsTo)");
+  TensorCT out;
+  out.width_ = packed.width_;
+  out.slotstr_ = packed.slotstr_;
+  out.num_ch_ = packed.num_ch_;
+  for (size_t grp = 0; grp < packed.ctks_.size(); ++grp)
+    for (PhantomCiphertext& c : unpack_channels(context_, plan, packed.ctks_[grp], plan.members(packed.num_ch_, grp), gk_))
+      out.ctks_.push_back(std::move(c));
+  return out;
+}
+
+TensorCT DNN::BootStrap(TensorCT& input, FHECKKSRNS& bootstrapper, size_t pack) {
+  const PackPlan plan = pack_plan(context_.poly_degree(), input.width_, input.slotstr_, pack);
+  check_uniform(input, "BootStrap");
+  if (plan.log_pack > bootstrapper.correction_factor())
+    throw std::invalid_argument("BootStrap: log2(pack) exceeds the bootstrapper's correction factor");
+  const uint32_t slots = static_cast<uint32_t>(plan.slots());
+  if (pack == 1) {
+    TensorCT result;
+    result.ctks_ = bootstrapper.EvalBootstrapBatch(input.ctks_, context_, 1, slots);
+    result.width_ = input.width_;
+    result.num_ch_ = input.num_ch_;
+    result.slotstr_ = input.slotstr_;
+    return result;
+  }
+  for (uint32_t e : plan.galois)
+    if (!gk_.has(e)) throw std::invalid_argument("BootStrap: no rotation key for a tree level (AddPackRotationsTo)");
+  // a degree-2 input is rescaled first, as the bootstrap does (RaiseWithCorrection)
+  TensorCT rescaled;
+  if (input.ctks_[0].GetNoiseScaleDeg() == 2) {
+    rescaled = input;
+    for (PhantomCiphertext& c : rescaled.ctks_) EvalModReduceInPlace(context_, c, 1);
+  }
+  PackedCT packed = Pack(rescaled.ctks_.empty() ? input : rescaled, pack);
+  packed.ctks_ = bootstrapper.EvalBootstrapBatch(packed.ctks_, context_, 1, slots, FHECKKSRNS::kBootGroup,
+                                                 static_cast<uint32_t>(plan.log_pack));
+  return Unpack(packed);
+}
+
+TensorCT DNN::Relu(const TensorCT& input, const PhantomRelinKey& relin_keys, int a, int b, int deg) {
+  check_uniform(input, "Relu");
+  if (deg < 1 || a >= b) throw std::invalid_argument("Relu: a < b and a degree of at least 1");
+  const std::vector<double> coefficients =
+      EvalChebyshevCoefficients([](double x) { return std::max(0.0, x); }, a, b, static_cast<uint32_t>(deg));
+  TensorCT result;
+  for (const PhantomCiphertext& c : input.ctks_)
+    result.ctks_.push_back(
+        EvalChebyshevSeries(context_, relin_keys, c, coefficients, a, b, m_scalingFactorsReal_, m_scalingFactorsRealBig_));
+  result.width_ = input.width_;
+  result.num_ch_ = input.num_ch_;
+  result.slotstr_ = input.slotstr_;
+  return result;
+}
+
+const std::vector<double>& DNN::SignCoefficients(size_t k) {
+  // src/dnn.cu:173-175
+  static const std::vector<std::vector<double>> rows = {
+      {0, 0.667972070856, 0, -0.223989523020, 0, 0.136121229346, 0, -0.099160550898, 0, 0.079224867308, 0, -0.067250088206,
+       0, 0.059852569462, 0, -0.503955481350},
+      {0, 0.955669291788, 0, -0.317870998995, 0, 0.189953989728, 0, -0.134924463410, 0, 0.104260767625, 0, -0.084798113265,
+       0, 0.071534728674, 0, -0.282024623439},
+      {0, 1.254717353059, 0, -0.371638622338, 0, 0.175181567419, 0, -0.085946606966, 0, 0.039326533561, 0, -0.015616729371,
+       0, 0.004903749402, 0, -0.000987938705}};
+  if (k > 2) throw std::invalid_argument("Sign: k must be 0, 1 or 2");
+  return rows[k];
+}
+
+double DNN::SignInterval(size_t k) {
+  if (k > 2) throw std::invalid_argument("Sign: k must be 0, 1 or 2");
+  return k == 0 ? 1.0 : k == 1 ? 1.908 : 1.332;
+}
+
+TensorCT DNN::Sign(const TensorCT& input, const PhantomRelinKey& relin_keys, size_t k) {
+  const std::vector<double>& coefficients = SignCoefficients(k);
+  const double b = SignInterval(k);
+  check_uniform(input, "Sign");
+  TensorCT result;
+  for (const PhantomCiphertext& c : input.ctks_)
+    result.ctks_.push_back(
+        EvalChebyshevSeries(context_, relin_keys, c, coefficients, -b, b, m_scalingFactorsReal_, m_scalingFactorsRealBig_));
+  result.width_ = input.width_;
+  result.num_ch_ = input.num_ch_;
+  result.slotstr_ = input.slotstr_;
+  return result;
+}
+
+TensorCT DNN::ReluDegTwo(const TensorCT& input, const PhantomRelinKey& relin_keys) {
+  check_uniform(input, "ReluDegTwo");
+  TensorCT result;
+  for (const PhantomCiphertext& c : input.ctks_) {
+    const PhantomCiphertext x2 = EvalSquare(context_, c, relin_keys, m_scalingFactorsReal_, m_scalingFactorsRealBig_);
+    result.ctks_.push_back(EvalAddAuto(context_, c, x2, m_scalingFactorsReal_, m_scalingFactorsRealBig_));
+  }
+  result.width_ = input.width_;
+  result.num_ch_ = input.num_ch_;
+  result.slotstr_ = input.slotstr_;
+  return result;
+}
+
+TensorCT DNN::ReluComposite(const TensorCT& input, FHECKKSRNS& bootstrapper, size_t pack) {
+  const PackPlan plan = pack_plan(context_.poly_degree(), input.width_, input.slotstr_, pack);
+  check_uniform(input, "ReluComposite");
+  if (plan.log_pack > bootstrapper.correction_factor())
+    throw std::invalid_argument("ReluComposite: log2(pack) exceeds the bootstrapper's correction factor");
+  TensorCT sign = input;
+  // scaled down so that it falls into [-1, 1]
+  for (PhantomCiphertext& c : sign.ctks_) EvalMultConstInplace(context_, c, 0.1, m_scalingFactorsReal_);
+  sign = Sign(sign, mul_key_, 0);
+  sign = BootStrap(sign, bootstrapper, pack);
+  sign = Sign(sign, mul_key_, 1);
+  sign = BootStrap(sign, bootstrapper, pack);
+  sign = Sign(sign, mul_key_, 2);
+  TensorCT result;
+  for (size_t i = 0; i < sign.num_ch_; ++i) {
+    EvalAddConstInPlaceWrap(context_, sign.ctks_[i], 1, m_scalingFactorsReal_, m_scalingFactorsRealBig_);
+    const PhantomCiphertext half = EvalMultConst(context_, input.ctks_[i], 0.5, m_scalingFactorsReal_);
+    result.ctks_.push_back(
+        EvalMultAuto(context_, sign.ctks_[i], half, mul_key_, m_scalingFactorsReal_, m_scalingFactorsRealBig_));
+  }
+  result.width_ = input.width_;
+  result.num_ch_ = input.num_ch_;
+  result.slotstr_ = input.slotstr_;
+  return BootStrap(result, bootstrapper, pack);
 }
 
 }  // namespace phantom

@@ -8,14 +8,20 @@
 // j width 4^slotstr slots, a whole row; the reference's width 2^slotstr 2^j (src/dnn.cu:334-338,
 // :421) is a row step only for slotstr = 0, where both agree.
 //
-// Not built here: Relu, ReluDegTwo, Sign, ReluComposite, SoftMax, BootStrap, the
-// weight loader and the ResNet driver.
+// BootStrap takes a pack: up to PackCapacity channels are interleaved into one ciphertext by monomial
+// shifts, bootstrapped once at pack x ns slots and taken apart by a rotation tree (host/pack.h), where
+// the reference bootstraps every channel on its own (src/dnn.cu:263-275, pack = 1 here).  Relu, Sign
+// and ReluDegTwo are the reference's channel loops; ReluComposite its sequence with the three
+// bootstrap loops going through BootStrap(.., pack).
+//
+// Not built here: SoftMax, the weight loader and the ResNet driver.
 #pragma once
 
 #include <cstdint>
 #include <memory>
 #include <vector>
 
+#include "bootstrap.h"
 #include "ciphertext.h"
 #include "ckks_eval.h"
 #include "context.h"
@@ -33,6 +39,16 @@ struct TensorCT {
   size_t width_ = 0;
   size_t slotstr_ = 0;
   size_t num_ch_ = 0;
+};
+
+// groups of up to pack_ channels interleaved by monomial shifts (host/pack.h): channel c is member
+// c % pack_ of ciphertext c / pack_
+struct PackedCT {
+  std::vector<PhantomCiphertext> ctks_;
+  size_t width_ = 0;
+  size_t slotstr_ = 0;
+  size_t num_ch_ = 0;
+  size_t pack_ = 1;
 };
 
 class DNN {
@@ -136,7 +152,42 @@ class DNN {
   // to the EvalMultConst / EvalAddAuto loop word for word, with the metadata rules above
   TensorCT MixChannels(const TensorCT& input, const std::vector<std::vector<double>>& weight);
 
+  // ---- the packed tensor bootstrap and the activation layers ----
+  // Every member below throws std::invalid_argument for channels at different levels, degrees or
+  // scales, a pack that is no power of two or above PackCapacity, log2(pack) above the bootstrapper's
+  // correction factor, k > 2, and a missing rotation key.
+  // min(N / (2 ns), 64) with ns = (width 2^slotstr)^2: the channels one ciphertext can hold
+  size_t PackCapacity(size_t width, size_t slotstr) const;
+  // appends the tree's rotations {ns 2^i : i < log2 pack} that the list lacks
+  void AddPackRotationsTo(std::vector<int32_t>& rotation_indices, size_t input_width, size_t slotstr, size_t pack);
+  // ceil(num_ch / pack) ciphertexts sum_c X^((lead + c) D) ct_c, D = N / (2 pack ns): no key switch, no
+  // level; level, degree and scale of the input.  lead = 0 for a full group and 1 otherwise: a group
+  // with a free index leaves index 0 free, where a bootstrap's slot-0 offset lands (host/pack.h)
+  PackedCT Pack(const TensorCT& input, size_t pack);
+  // the rotation tree (pack - 1 key switches for a full group): level, degree and scale() of the packed
+  // input; every channel's message is pack_ times the packed one's
+  TensorCT Unpack(const PackedCT& packed);
+  // pack = 1: every channel through EvalBootstrapBatch at ns slots (src/dnn.cu:263-275).  pack = P > 1:
+  // rescale a degree-2 input, Pack, EvalBootstrapBatch of the groups at P ns slots with
+  // post_shift = log2 P (the tree's factor P is taken out of the bootstrap's closing integer: no
+  // precision, no level), Unpack.  The result has the level EvalBootstrap returns for P ns slots,
+  // degree 1 and its scale.  The bootstrapper must be set up and keyed for P ns slots, and the
+  // model's Galois key must hold the pack rotations (AddPackRotationsTo).
+  TensorCT BootStrap(TensorCT& input, FHECKKSRNS& bootstrapper, size_t pack = 1);
+  // EvalChebyshevSeries of max(0, x) on [a, b] per channel (src/dnn.cu:152-168)
+  TensorCT Relu(const TensorCT& input, const PhantomRelinKey& relin_keys, int a = -1, int b = 1, int deg = 7);
+  // stage k <= 2 of the composite sign approximation per channel (src/dnn.cu:170-191)
+  TensorCT Sign(const TensorCT& input, const PhantomRelinKey& relin_keys, size_t k);
+  static const std::vector<double>& SignCoefficients(size_t k);  // the stage's series, c_0 not halved
+  static double SignInterval(size_t k);                         // its interval is [-v, v]
+  // x + x^2 per channel (src/dnn.cu:247-261)
+  TensorCT ReluDegTwo(const TensorCT& input, const PhantomRelinKey& relin_keys);
+  // 0.5 x (1 + sign(0.1 x)) with the three sign stages, a bootstrap after the first two and at the end
+  // (src/dnn.cu:193-243), each through BootStrap(.., pack); uses the model's RelinKeyGen key
+  TensorCT ReluComposite(const TensorCT& input, FHECKKSRNS& bootstrapper, size_t pack = 1);
+
  private:
+  void check_uniform(const TensorCT& input, const char* who) const;
   // the layer on dev_W (conv2d_raw), or on `plan` when it is not null (conv2d_apply)
   TensorCT conv_run(const TensorCT& input, const double* dev_W, const ConvPlanData* plan, size_t kernel_h, size_t out_ch,
                     size_t stride);

@@ -143,6 +143,10 @@ _SIGS = {
                                           ctypes.POINTER(ctypes.POINTER(vp)), ctypes.POINTER(ctypes.POINTER(vp)), sz,
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(vp), vp]),
+    "phantom_pack_rotations": (ctypes.c_int, [sz, sz, sz, sz, vp, vp, vp, sz, ctypes.POINTER(sz)]),
+    "phantom_ct_pack": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, ctypes.c_uint32, vp, vp]),
+    "phantom_ct_split": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ctypes.c_uint32,
+                                        ctypes.POINTER(vp), ctypes.POINTER(vp), vp]),
     "phantom_conv_rotations": (ctypes.c_int, [sz, sz, sz, vp, sz, ctypes.POINTER(sz)]),
     "phantom_conv_weight_slots": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp, vp]),
     "phantom_conv_weight_slots_host": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp]),
