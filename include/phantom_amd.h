@@ -360,6 +360,43 @@ int phantom_conv_plan_destroy(phantom_conv_plan *plan);
 int phantom_conv2d_apply(const phantom_context *ctx, const phantom_conv_plan *plan, const uint64_t *const *cts,
                          const uint64_t *const *const *key_digits, size_t dnum, const uint32_t *galois_elts,
                          uint64_t *const *outs, hipStream_t stream);
+/* Batch norm, bias and the residual add fused into a prepared layer.  All three are affine in the
+ * layer's output: the scale a_h is folded into the weights, and the two additions enter the inner
+ * sum in the extended basis as P (m res_h + B_h), which is 0 modulo P and so passes through the
+ * moddown exactly: the result is the unseeded entry's plus (m res_h + [polynomial 0] B_h) mod q_l,
+ * word for word, at no extra level, launch or pass over memory.
+ *   phantom_ext_mac_sub_seeded: phantom_ext_mac_sub (accumulate = 0) whose sum of output o,
+ *     polynomial p, limb l < Ql starts at P (res[o][p][l][e] res_mult[l] + [p == 0] bias[o][l]) mod q_l
+ *     and at 0 on the limbs of P.  res: host array [O] of device [2][Ql][N] ciphertexts (limb stride
+ *     Ql; entries may be null, or res itself); res_mult: host [Ql], required with res; bias: host
+ *     [O][Ql], or null.  All residues are taken modulo q_l here.
+ *   phantom_conv2d_prepare_scaled: phantom_conv2d_prepare with the weights of output channel h
+ *     multiplied by out_scale[h] (host [out_ch], null: 1.0) in FP64 on the device before the encode;
+ *     dev_W is not modified.
+ *   phantom_conv2d_apply_seeded: phantom_conv2d_apply with res (host [out_ch], at the plan's chain
+ *     index), res_mult (host [Ql], m mod q_l) and bias (host [out_ch][Ql], B_h mod q_l) as above.
+ *   phantom_scaled_constant_residues: round(value scale) mod moduli[i], i < count, on the host (no
+ *     device is touched): the B_h of a bias at a scale that may exceed 2^64; a negative constant gives
+ *     q - (|B| mod q).
+ * Refused (status 1, outputs untouched): what the unseeded entries refuse, res without res_mult, an
+ * out_scale that is not finite; a product that is not finite, a scale that is not positive, a zero
+ * modulus. */
+int phantom_ext_mac_sub_seeded(const phantom_context *ctx, size_t chain_index, const uint64_t *const *ins, size_t T,
+                               const uint64_t *const *dev_pts, size_t sub_degree, size_t O, uint64_t *const *outs,
+                               const uint64_t *const *res, const uint64_t *res_mult, const uint64_t *bias,
+                               hipStream_t stream);
+int phantom_conv2d_prepare_scaled(const phantom_context *ctx, size_t chain_index, size_t in_ch, size_t out_ch,
+                                  size_t width, size_t slotstr, size_t kernel, const double *dev_W,
+                                  const double *out_scale, double pt_scale, int *dev_overflow, hipStream_t stream,
+                                  phantom_conv_plan **plan);
+int phantom_conv2d_apply_seeded(const phantom_context *ctx, const phantom_conv_plan *plan, const uint64_t *const *cts,
+                                const uint64_t *const *const *key_digits, size_t dnum, const uint32_t *galois_elts,
+                                uint64_t *const *outs, const uint64_t *const *res, const uint64_t *res_mult,
+                                const uint64_t *bias, hipStream_t stream);
+/* the plan's plaintext words copied to host_out (capacity in words, at least phantom_conv_plan_bytes / 8);
+ * waits for the device */
+int phantom_conv_plan_read(const phantom_conv_plan *plan, uint64_t *host_out, size_t capacity);
+int phantom_scaled_constant_residues(double value, double scale, const uint64_t *moduli, size_t count, uint64_t *out);
 
 /* ---- hoisted average pooling + fully connected layer (DNN::AvgPoolFullCon, src/dnn.cu:397-452) ----
  * The reference pools each of the t input channels by 2 log2(width) sequential EvalRotateFused +

@@ -134,9 +134,10 @@ int phantom_conv2d(const phantom_context* ctx, size_t chain_index, const uint64_
   });
 }
 
-int phantom_ext_mac_sub(const phantom_context* ctx, size_t chain_index, const uint64_t* const* ins, size_t T,
-                        const uint64_t* const* dev_pts, size_t sub_degree, size_t O, uint64_t* const* outs,
-                        int accumulate, hipStream_t stream) {
+static int ext_mac_sub_run(const phantom_context* ctx, size_t chain_index, const uint64_t* const* ins, size_t T,
+                           const uint64_t* const* dev_pts, size_t sub_degree, size_t O, uint64_t* const* outs,
+                           int accumulate, const uint64_t* const* res, const uint64_t* res_mult, const uint64_t* bias,
+                           hipStream_t stream) {
   PHX_CAPI_GUARD({
     const auto& pc = phantom_capi_context(ctx);
     if (!ins || !dev_pts || !outs) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
@@ -144,6 +145,7 @@ int phantom_ext_mac_sub(const phantom_context* ctx, size_t chain_index, const ui
       return fail(PHANTOM_ERR_INVALID_ARGUMENT, "term and output counts must be at least 1");
     if (sub_degree == 0 || sub_degree > pc.poly_degree() || (sub_degree & (sub_degree - 1)))
       return fail(PHANTOM_ERR_INVALID_ARGUMENT, "the subring degree must be a power of two in [1, N]");
+    if (res && !res_mult) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "a residual needs its multiplier");
     phx::MacArgs a = phantom::mac_args(pc, chain_index);
     // one device table: the T input pointers, then the O output pointers
     std::vector<uint64_t*> tab(T + O);
@@ -163,15 +165,51 @@ int phantom_ext_mac_sub(const phantom_context* ctx, size_t chain_index, const ui
     a.T = static_cast<uint32_t>(T);
     a.O = static_cast<uint32_t>(O);
     a.accumulate = accumulate != 0;
+    phantom::DeviceBuffer<uint64_t> seed;
+    if (res || bias) {
+      seed.allocate(phantom::mac_seed_words(O, a.Ql), stream);
+      phantom::mac_seed(pc, chain_index, O, res, res_mult, bias, seed.get(), a, stream);
+    }
     const hipError_t e = phx::ext_mac_sub(a, pc.poly_degree(), sub_degree, stream);
-    PHX_CHECK(hipStreamSynchronize(stream));  // the pointer table is freed on return
+    PHX_CHECK(hipStreamSynchronize(stream));  // the tables are freed on return
     return from_hip(e);
+  });
+}
+
+int phantom_ext_mac_sub(const phantom_context* ctx, size_t chain_index, const uint64_t* const* ins, size_t T,
+                        const uint64_t* const* dev_pts, size_t sub_degree, size_t O, uint64_t* const* outs,
+                        int accumulate, hipStream_t stream) {
+  return ext_mac_sub_run(ctx, chain_index, ins, T, dev_pts, sub_degree, O, outs, accumulate, nullptr, nullptr, nullptr,
+                         stream);
+}
+
+int phantom_ext_mac_sub_seeded(const phantom_context* ctx, size_t chain_index, const uint64_t* const* ins, size_t T,
+                               const uint64_t* const* dev_pts, size_t sub_degree, size_t O, uint64_t* const* outs,
+                               const uint64_t* const* res, const uint64_t* res_mult, const uint64_t* bias,
+                               hipStream_t stream) {
+  return ext_mac_sub_run(ctx, chain_index, ins, T, dev_pts, sub_degree, O, outs, 0, res, res_mult, bias, stream);
+}
+
+int phantom_scaled_constant_residues(double value, double scale, const uint64_t* moduli, size_t count, uint64_t* out) {
+  PHX_CAPI_GUARD({
+    if (!moduli || !out) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    const std::vector<uint64_t> r = phantom::scaled_constant_residues(value, scale, moduli, count);
+    for (size_t i = 0; i < count; ++i) out[i] = r[i];
+    return PHANTOM_OK;
   });
 }
 
 int phantom_conv2d_prepare(const phantom_context* ctx, size_t chain_index, size_t in_ch, size_t out_ch, size_t width,
                            size_t slotstr, size_t kernel, const double* dev_W, double pt_scale, int* dev_overflow,
                            hipStream_t stream, phantom_conv_plan** plan) {
+  return phantom_conv2d_prepare_scaled(ctx, chain_index, in_ch, out_ch, width, slotstr, kernel, dev_W, nullptr, pt_scale,
+                                       dev_overflow, stream, plan);
+}
+
+int phantom_conv2d_prepare_scaled(const phantom_context* ctx, size_t chain_index, size_t in_ch, size_t out_ch,
+                                  size_t width, size_t slotstr, size_t kernel, const double* dev_W,
+                                  const double* out_scale, double pt_scale, int* dev_overflow, hipStream_t stream,
+                                  phantom_conv_plan** plan) {
   PHX_CAPI_GUARD({
     const auto& pc = phantom_capi_context(ctx);
     if (!dev_W || !plan) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
@@ -179,7 +217,7 @@ int phantom_conv2d_prepare(const phantom_context* ctx, size_t chain_index, size_
     (void)phantom::mac_args(pc, chain_index);
     const phx::ConvShape c = phantom::conv_shape(pc.poly_degree(), width, slotstr, kernel, in_ch, out_ch);
     auto p = std::make_unique<phantom_conv_plan>();
-    p->data = phantom::conv2d_prepare(pc, chain_index, c, dev_W, pt_scale, dev_overflow, stream);
+    p->data = phantom::conv2d_prepare(pc, chain_index, c, dev_W, pt_scale, dev_overflow, stream, out_scale);
     p->owner = ctx;
     *plan = p.release();
     return PHANTOM_OK;
@@ -194,6 +232,16 @@ int phantom_conv_plan_bytes(const phantom_conv_plan* plan, size_t* bytes) {
   });
 }
 
+int phantom_conv_plan_read(const phantom_conv_plan* plan, uint64_t* host_out, size_t capacity) {
+  PHX_CAPI_GUARD({
+    if (!plan || !host_out) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (capacity < plan->data->words) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "capacity below the plan's words");
+    PHX_CHECK(hipDeviceSynchronize());
+    PHX_CHECK(hipMemcpy(host_out, plan->data->pts, plan->data->bytes(), hipMemcpyDeviceToHost));
+    return PHANTOM_OK;
+  });
+}
+
 int phantom_conv_plan_destroy(phantom_conv_plan* plan) {
   PHX_CAPI_GUARD({
     delete plan;
@@ -204,10 +252,19 @@ int phantom_conv_plan_destroy(phantom_conv_plan* plan) {
 int phantom_conv2d_apply(const phantom_context* ctx, const phantom_conv_plan* plan, const uint64_t* const* cts,
                          const uint64_t* const* const* key_digits, size_t dnum, const uint32_t* galois_elts,
                          uint64_t* const* outs, hipStream_t stream) {
+  return phantom_conv2d_apply_seeded(ctx, plan, cts, key_digits, dnum, galois_elts, outs, nullptr, nullptr, nullptr,
+                                     stream);
+}
+
+int phantom_conv2d_apply_seeded(const phantom_context* ctx, const phantom_conv_plan* plan, const uint64_t* const* cts,
+                                const uint64_t* const* const* key_digits, size_t dnum, const uint32_t* galois_elts,
+                                uint64_t* const* outs, const uint64_t* const* res, const uint64_t* res_mult,
+                                const uint64_t* bias, hipStream_t stream) {
   PHX_CAPI_GUARD({
     const auto& pc = phantom_capi_context(ctx);
     if (!plan || !cts || !key_digits || !galois_elts || !outs)
       return fail(PHANTOM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (res && !res_mult) return fail(PHANTOM_ERR_INVALID_ARGUMENT, "a residual needs its multiplier");
     if (plan->owner != ctx || plan->data->ctx != &pc)
       return fail(PHANTOM_ERR_INVALID_ARGUMENT, "the plan was prepared for another context");
     const phx::ConvShape& c = plan->data->shape;
@@ -224,7 +281,7 @@ int phantom_conv2d_apply(const phantom_context* ctx, const phantom_conv_plan* pl
     std::vector<const uint64_t* const*> evk(K2, nullptr);
     for (size_t t = 0; t < K2; ++t)
       if (key_digits[t]) evk[t] = phantom_capi_key_array(ctx, key_digits[t], dnum, beta);
-    phantom::conv2d_apply(pc, *plan->data, cts, evk.data(), galois_elts, outs, stream);
+    phantom::conv2d_apply(pc, *plan->data, cts, evk.data(), galois_elts, outs, stream, res, res_mult, bias);
     return PHANTOM_OK;
   });
 }

@@ -33,7 +33,7 @@ namespace phx {
 // one-element-per-thread form.
 constexpr int kMacBlock = 32, kMacWaves = 8, kMacEpl = 2, kMacTile = 64 * kMacEpl;
 constexpr size_t kMacTileMinN = 1024;
-struct MacArgs {
+struct MacCore {
   const uint64_t* const* ins = nullptr;  // device table [T], or
   const uint64_t* in0 = nullptr;
   uint64_t in_stride = 0;
@@ -49,6 +49,29 @@ struct MacArgs {
   uint32_t q60 = 0;         // as LtArgs::q60
   uint32_t accumulate = 0;  // add the value already in out[o] (below q)
 };
+struct MacArgs : MacCore {
+  // optional seed (below); all three null: no seed
+  const uint64_t* const* seed_res = nullptr;  // device table [O] of [2][Ql][n] ciphertexts; entries may be null
+  const uint64_t* seed_mult = nullptr;        // device [Ql], required with seed_res
+  const uint64_t* seed_bias = nullptr;        // device [O][Ql]
+};
+// ---- the seed: an affine term entering the sum in the extended basis --------------------------
+// With seed_res or seed_bias set, the sum of output o, polynomial p, limb l, element e starts at
+//   l < Ql:   (seed_res[o] ? seed_res[o][p][l][e] seed_mult[l] : 0) + (p == 0 && seed_bias ? seed_bias[o][l] : 0)  (mod q_l)
+//   l >= Ql:  0                                                                      (the limbs of P)
+// instead of 0.  The residuals are ciphertexts over Ql (limb stride Ql, not Ql + P) with words below
+// q_l, read with the kernel's 16-byte accesses; seed_mult and seed_bias hold residues below q_l.  A
+// caller that passes (m P) mod q_l and (B_o P) mod q_l adds P (m res_o + [p == 0] B_o), which is
+// 0 modulo P, so the moddown of the result is moddown(sum) + m res_o + [p == 0] B_o word for word
+// (DESIGN.md §3 "Fused affine terms").  The seed is reduced below q (one Barrett product, one
+// conditional subtraction) before it enters the 128-bit sum, where it takes the place of
+// `accumulate`'s old value: the bound q + 32 q^2 < 2^127 + 2^61 and the folding schedule above hold
+// as written.  A seed together with accumulate, and seed_res without seed_mult, are refused
+// (hipErrorInvalidValue).  Both ext_mac and ext_mac_sub take a seed, in the tiled and the plain form.
+// The kernels take MacCore by value and the seed as a trailing argument of their seeded instantiations
+// only, so a launch without a seed has the signature, the arguments and the code it had before seeds
+// existed, and every seeded instantiation keeps its twin's registers and uses no scratch on gfx950
+// (DESIGN.md §3).
 hipError_t ext_mac(const MacArgs& a, size_t n, hipStream_t s);
 
 // ---- the same sums over compact plaintexts ---------------------------------------------------
@@ -75,6 +98,8 @@ hipError_t ext_mac_sub(const MacArgs& a, size_t n, size_t sub_degree, hipStream_
 // written as interleaved (re, 0): the slot at (r Lg + c) pow, r, c < width, is W[a][b][k][h] when
 // r + a - K/2 and c + b - K/2 both lie in [0, width), every other slot 0 (src/dnn.cu:103-113).
 // Terms are ordered (h, k, a, b), b fastest; `count` terms from `first_term` go to out [count][ns].
+// dev_out_scale (device [out_ch], null: none): the terms of output channel h are multiplied by
+// dev_out_scale[h] in FP64, one rounding per weight (a batch norm's scale folded into the layer).
 struct ConvShape {
   uint32_t width = 0, slotstr = 0, kernel = 0, in_ch = 0, out_ch = 0;
   size_t large() const { return static_cast<size_t>(width) << slotstr; }
@@ -82,7 +107,7 @@ struct ConvShape {
   size_t terms() const { return static_cast<size_t>(out_ch) * in_ch * kernel * kernel; }
 };
 hipError_t conv_weight_slots(const ConvShape& c, const double* dev_W, size_t first_term, size_t count, double* dev_out,
-                             hipStream_t s);
+                             hipStream_t s, const double* dev_out_scale = nullptr);
 void conv_weight_slots_host(const ConvShape& c, const double* W, size_t first_term, size_t count, double* out);
 
 // `count` (<= kWordsMax) 64-bit words passed by value written to dst: small device tables built

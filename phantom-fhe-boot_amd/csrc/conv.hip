@@ -11,14 +11,24 @@ namespace {
 constexpr int kBlock = 256;
 constexpr uint64_t kM30 = (1ull << 30) - 1;
 
+// The kernels take the operand lists and moduli (MacCore) and, in their seeded instantiations only,
+// the seed as a trailing argument (`Seed...` is empty or one MacSeed): without a seed the kernel has
+// the signature, the arguments and the code it had before seeds existed.
+struct MacSeed {
+  const uint64_t* const* res;
+  const uint64_t* mult;
+  const uint64_t* bias;
+};
+__device__ __forceinline__ const MacSeed& mac_the_seed(const MacSeed& sd) { return sd; }
+
 // operand k of a list given as a device pointer table or as base + k stride
-__device__ __forceinline__ const uint64_t* mac_in(const MacArgs& a, uint32_t t) {
+__device__ __forceinline__ const uint64_t* mac_in(const MacCore& a, uint32_t t) {
   return a.ins ? a.ins[t] : a.in0 + static_cast<size_t>(t) * a.in_stride;
 }
-__device__ __forceinline__ const uint64_t* mac_pt(const MacArgs& a, size_t k) {
+__device__ __forceinline__ const uint64_t* mac_pt(const MacCore& a, size_t k) {
   return a.pts ? a.pts[k] : a.pt0 + k * a.pt_stride;
 }
-__device__ __forceinline__ uint64_t* mac_out(const MacArgs& a, uint32_t o) {
+__device__ __forceinline__ uint64_t* mac_out(const MacCore& a, uint32_t o) {
   return a.outs ? a.outs[o] : a.out0 + static_cast<size_t>(o) * a.out_stride;
 }
 
@@ -50,9 +60,17 @@ __device__ __forceinline__ void mac_fold(u128& acc, MacPart& P) {
 
 constexpr int kMacChunk = 4, kMacChunks = kMacBlock / kMacChunk;
 
+// the seed of one word (conv.h): x seed_mult[l] (x the residual's word, when output o has one) plus
+// the bias residue (polynomial 0 only), below q
+__device__ __forceinline__ uint64_t mac_seed(bool has_res, uint64_t x, uint64_t mult, uint64_t bias, uint64_t q,
+                                             uint64_t r0, uint64_t r1) {
+  const uint64_t v = has_res ? mul_mod(x, mult, q, r0, r1) : 0;
+  return add_mod(v, bias, q);
+}
+
 // chunk c (terms 4c .. 4c + 3 of the block at t0) of output o's plaintexts; terms past the last
 // read the last one again (their inputs are staged as zeros)
-__device__ __forceinline__ void mac_load_chunk(MacVec (&w)[kMacChunk], const MacArgs& a, size_t prow, uint32_t t0, int c,
+__device__ __forceinline__ void mac_load_chunk(MacVec (&w)[kMacChunk], const MacCore& a, size_t prow, uint32_t t0, int c,
                                                size_t e) {
 #pragma unroll
   for (int j = 0; j < kMacChunk; ++j) {
@@ -91,8 +109,10 @@ __device__ __forceinline__ void mac_chunk_products(MacPart (&part)[kMacEpl][2], 
 // as 30-bit halves; then each wave with an output streams that output's 32 plaintexts 4 at a time,
 // chunk c + 1's loads in flight while chunk c's products run.  The 128-bit sums stay in registers
 // and are reduced below q after every block (conv.h).
-template <bool Q60>
-__global__ __launch_bounds__(64 * kMacWaves) void ext_mac_tile_kernel(MacArgs a, uint32_t log_n, size_t total) {
+template <bool Q60, class... Seed>
+__global__ __launch_bounds__(64 * kMacWaves) void ext_mac_tile_kernel(MacCore a, uint32_t log_n, size_t total,
+                                                                      Seed... seed) {
+  constexpr bool Seeded = sizeof...(Seed) != 0;
   constexpr int E = kMacEpl;
   __shared__ uint2 xs[2 * kMacBlock][kMacTile];
   const int lane = threadIdx.x & 63;
@@ -116,7 +136,23 @@ __global__ __launch_bounds__(64 * kMacWaves) void ext_mac_tile_kernel(MacArgs a,
       acc[k][p] = u128{0, 0};
       part[k][p] = MacPart{0, 0, 0, 0};
     }
-  if (active && a.accumulate) {
+  if constexpr (Seeded) {
+    // the seed takes accumulate's place: limbs of Ql only, below q (conv.h)
+    if (active && l < static_cast<int>(a.Ql)) {
+      const MacSeed& sd = mac_the_seed(seed...);
+      const uint64_t* const res = sd.res ? sd.res[o] : nullptr;  // wave-uniform
+      const uint64_t mult = res ? sd.mult[l] : 0;
+      const uint64_t bias = sd.bias ? sd.bias[static_cast<size_t>(o) * a.Ql + l] : 0;
+      const size_t res_total = static_cast<size_t>(a.Ql) << log_n;
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        MacVec x{{0, 0}};
+        if (res) x = mac_ld(res + p * res_total + e);
+#pragma unroll
+        for (int k = 0; k < E; ++k) acc[k][p].lo = mac_seed(res != nullptr, x.v[k], mult, p == 0 ? bias : 0, q, r0, r1);
+      }
+    }
+  } else if (active && a.accumulate) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const MacVec old = mac_ld(op + p * total + e);
@@ -187,7 +223,9 @@ __global__ __launch_bounds__(64 * kMacWaves) void ext_mac_tile_kernel(MacArgs a,
 // One element per thread and grid-stride step, grid row y = output y: any n and any tile
 // alignment.  Terms 4 at a time (4 products per partial sum fit for every modulus below 2^61),
 // the 128-bit sum reduced below q every kMacBlock terms.
-__global__ __launch_bounds__(kBlock) void ext_mac_plain_kernel(MacArgs a, uint32_t log_n, size_t total) {
+template <class... Seed>
+__global__ __launch_bounds__(kBlock) void ext_mac_plain_kernel(MacCore a, uint32_t log_n, size_t total, Seed... seed) {
+  constexpr bool Seeded = sizeof...(Seed) != 0;
   const uint32_t o = blockIdx.y;
   uint64_t* const op = mac_out(a, o);
   const size_t prow = static_cast<size_t>(o) * a.T;
@@ -196,7 +234,17 @@ __global__ __launch_bounds__(kBlock) void ext_mac_plain_kernel(MacArgs a, uint32
     const int row = l < static_cast<int>(a.Ql) ? l : static_cast<int>(a.size_Q) + (l - static_cast<int>(a.Ql));
     const uint64_t q = a.q[row], r0 = a.barrett[2 * row], r1 = a.barrett[2 * row + 1];
     u128 acc[2] = {{0, 0}, {0, 0}};
-    if (a.accumulate) {
+    if constexpr (Seeded) {
+      if (l < static_cast<int>(a.Ql)) {
+        const MacSeed& sd = mac_the_seed(seed...);
+        const uint64_t* const res = sd.res ? sd.res[o] : nullptr;
+        const uint64_t mult = res ? sd.mult[l] : 0;
+        const uint64_t bias = sd.bias ? sd.bias[static_cast<size_t>(o) * a.Ql + l] : 0;
+        const size_t res_total = static_cast<size_t>(a.Ql) << log_n;
+        acc[0].lo = mac_seed(res != nullptr, res ? res[e] : 0, mult, bias, q, r0, r1);
+        acc[1].lo = mac_seed(res != nullptr, res ? res[res_total + e] : 0, mult, 0, q, r0, r1);
+      }
+    } else if (a.accumulate) {
       acc[0].lo = op[e];
       acc[1].lo = op[total + e];
     }
@@ -232,7 +280,7 @@ __global__ __launch_bounds__(kBlock) void ext_mac_plain_kernel(MacArgs a, uint32
 // chunk c of output o's plaintext words, one per lane (shared by the lane's two elements); byte
 // offset `pofs` from each plaintext's base, 32 bits so that the load takes the scalar base and a
 // vector offset
-__device__ __forceinline__ void sub_load_chunk(uint64_t (&w)[kMacChunk], const MacArgs& a, size_t prow, uint32_t t0,
+__device__ __forceinline__ void sub_load_chunk(uint64_t (&w)[kMacChunk], const MacCore& a, size_t prow, uint32_t t0,
                                                int c, uint32_t pofs) {
 #pragma unroll
   for (int j = 0; j < kMacChunk; ++j) {
@@ -287,9 +335,11 @@ constexpr int kSubRows = 2 * kMacBlock / kSubWaves;
 __device__ __forceinline__ MacVec sub_ld2(const uint64_t* base, uint32_t ofs) {
   return mac_ld(reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(base) + ofs));
 }
-template <bool Q60, bool Uniform>
-__global__ __launch_bounds__(64 * kSubWaves) void ext_mac_sub_tile_kernel(MacArgs a, uint32_t log_n, uint32_t log_g,
-                                                                          uint32_t rows, size_t total) {
+template <bool Q60, bool Uniform, class... Seed>
+__global__ __launch_bounds__(64 * kSubWaves) void ext_mac_sub_tile_kernel(MacCore a, uint32_t log_n, uint32_t log_g,
+                                                                          uint32_t rows, size_t total,
+                                                                          Seed... seed) {
+  constexpr bool Seeded = sizeof...(Seed) != 0;
   constexpr int E = kMacEpl;
   __shared__ uint2 xs[2 * kMacBlock][kMacTile];
   const int lane = threadIdx.x & 63;
@@ -319,7 +369,24 @@ __global__ __launch_bounds__(64 * kSubWaves) void ext_mac_sub_tile_kernel(MacArg
       acc[k][p] = u128{0, 0};
       part[k][p] = MacPart{0, 0, 0, 0};
     }
-  if (active && a.accumulate) {
+  if constexpr (Seeded) {
+    // the seed takes accumulate's place: limbs of Ql only, below q (conv.h).  It is formed before the
+    // first rows are requested, so it adds nothing to the registers live in the loop.
+    if (active && l < static_cast<int>(a.Ql)) {
+      const MacSeed& sd = mac_the_seed(seed...);
+      const uint64_t* const res = sd.res ? sd.res[o] : nullptr;  // wave-uniform
+      const uint64_t mult = res ? sd.mult[l] : 0;
+      const uint64_t bias = sd.bias ? sd.bias[static_cast<size_t>(o) * a.Ql + l] : 0;
+      const size_t res_total = static_cast<size_t>(a.Ql) << log_n;
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        MacVec x{{0, 0}};
+        if (res) x = sub_ld2(res + p * res_total + e0, lofs);
+#pragma unroll
+        for (int k = 0; k < E; ++k) acc[k][p].lo = mac_seed(res != nullptr, x.v[k], mult, p == 0 ? bias : 0, q, r0, r1);
+      }
+    }
+  } else if (active && a.accumulate) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const MacVec old = sub_ld2(op + p * total + e0, lofs);
@@ -394,8 +461,10 @@ __global__ __launch_bounds__(64 * kSubWaves) void ext_mac_sub_tile_kernel(MacArg
 }
 
 // ext_mac_plain_kernel with the plaintext word of element e of limb l at l (n >> log_g) + (e >> log_g)
-__global__ __launch_bounds__(kBlock) void ext_mac_sub_plain_kernel(MacArgs a, uint32_t log_n, uint32_t log_g,
-                                                                   size_t total) {
+template <class... Seed>
+__global__ __launch_bounds__(kBlock) void ext_mac_sub_plain_kernel(MacCore a, uint32_t log_n, uint32_t log_g,
+                                                                   size_t total, Seed... seed) {
+  constexpr bool Seeded = sizeof...(Seed) != 0;
   const uint32_t o = blockIdx.y;
   uint64_t* const op = mac_out(a, o);
   const size_t prow = static_cast<size_t>(o) * a.T;
@@ -406,7 +475,17 @@ __global__ __launch_bounds__(kBlock) void ext_mac_sub_plain_kernel(MacArgs a, ui
     const uint64_t q = a.q[row], r0 = a.barrett[2 * row], r1 = a.barrett[2 * row + 1];
     const size_t poff = (static_cast<size_t>(l) << (log_n - log_g)) + ((e & n1) >> log_g);
     u128 acc[2] = {{0, 0}, {0, 0}};
-    if (a.accumulate) {
+    if constexpr (Seeded) {
+      if (l < static_cast<int>(a.Ql)) {
+        const MacSeed& sd = mac_the_seed(seed...);
+        const uint64_t* const res = sd.res ? sd.res[o] : nullptr;
+        const uint64_t mult = res ? sd.mult[l] : 0;
+        const uint64_t bias = sd.bias ? sd.bias[static_cast<size_t>(o) * a.Ql + l] : 0;
+        const size_t res_total = static_cast<size_t>(a.Ql) << log_n;
+        acc[0].lo = mac_seed(res != nullptr, res ? res[e] : 0, mult, bias, q, r0, r1);
+        acc[1].lo = mac_seed(res != nullptr, res ? res[res_total + e] : 0, mult, 0, q, r0, r1);
+      }
+    } else if (a.accumulate) {
       acc[0].lo = op[e];
       acc[1].lo = op[total + e];
     }
@@ -439,8 +518,9 @@ __global__ __launch_bounds__(kBlock) void ext_mac_sub_plain_kernel(MacArgs a, ui
 }
 
 // thread i: slot i % ns of term first + i / ns
-__global__ __launch_bounds__(kBlock) void conv_weight_slots_kernel(ConvShape c, const double* W, size_t first, size_t total,
-                                                                   uint32_t log_ns, double2* out) {
+__global__ __launch_bounds__(kBlock) void conv_weight_slots_kernel(ConvShape c, const double* W, const double* out_scale,
+                                                                   size_t first, size_t total, uint32_t log_ns,
+                                                                   double2* out) {
   const uint32_t K = c.kernel, half = K / 2, lg = c.width << c.slotstr;
   const uint32_t log_lg = log_ns / 2;
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kBlock) {
@@ -457,7 +537,7 @@ __global__ __launch_bounds__(kBlock) void conv_weight_slots_kernel(ConvShape c, 
       // r + a - K/2 and col + b - K/2 in [0, width)
       if (r < c.width && col < c.width && r + ta >= half && r + ta < half + c.width && col + b >= half &&
           col + b < half + c.width)
-        v = W[((static_cast<size_t>(ta) * K + b) * c.in_ch + k) * c.out_ch + h];
+        v = W[((static_cast<size_t>(ta) * K + b) * c.in_ch + k) * c.out_ch + h] * (out_scale ? out_scale[h] : 1.0);
     }
     out[i] = make_double2(v, 0.0);
   }
@@ -469,22 +549,38 @@ __global__ __launch_bounds__(64) void write_words_kernel(uint64_t* dst, Words w,
 
 unsigned grid_for(size_t total) { return static_cast<unsigned>(std::min<size_t>((total + kBlock - 1) / kBlock, 65535)); }
 
+// a seed with accumulate, or a residual table without its multiplier, is refused
+bool mac_seeded(const MacArgs& a) { return a.seed_res || a.seed_bias; }
+bool mac_seed_ok(const MacArgs& a) { return !(mac_seeded(a) && a.accumulate) && !(a.seed_res && !a.seed_mult); }
+
 }  // namespace
 
 hipError_t ext_mac(const MacArgs& a, size_t n, hipStream_t s) {
   if (a.T == 0 || a.O == 0 || n == 0 || (n & (n - 1))) return hipErrorInvalidValue;
   if ((!a.ins && !a.in0) || (!a.pts && !a.pt0) || (!a.outs && !a.out0)) return hipErrorInvalidValue;
+  if (!mac_seed_ok(a)) return hipErrorInvalidValue;
+  const bool seeded = mac_seeded(a);
+  const MacCore& core = a;
+  const MacSeed sd{a.seed_res, a.seed_mult, a.seed_bias};
   const size_t total = static_cast<size_t>(a.Ql + a.P) * n;
   const uint32_t log_n = static_cast<uint32_t>(__builtin_ctzll(n));
   if (n >= kMacTileMinN && n % kMacTile == 0) {
     // a tile never crosses a limb (n is a multiple of it)
     const dim3 grid(static_cast<unsigned>(total / kMacTile), (a.O + kMacWaves - 1) / kMacWaves);
     if (grid.y > 65535) return hipErrorInvalidValue;
-    if (a.q60) ext_mac_tile_kernel<true><<<grid, 64 * kMacWaves, 0, s>>>(a, log_n, total);
-    else ext_mac_tile_kernel<false><<<grid, 64 * kMacWaves, 0, s>>>(a, log_n, total);
+    const unsigned threads = 64 * kMacWaves;
+    if (a.q60) {
+      if (seeded) ext_mac_tile_kernel<true, MacSeed><<<grid, threads, 0, s>>>(core, log_n, total, sd);
+      else ext_mac_tile_kernel<true><<<grid, threads, 0, s>>>(core, log_n, total);
+    } else {
+      if (seeded) ext_mac_tile_kernel<false, MacSeed><<<grid, threads, 0, s>>>(core, log_n, total, sd);
+      else ext_mac_tile_kernel<false><<<grid, threads, 0, s>>>(core, log_n, total);
+    }
   } else {
     if (a.O > 65535) return hipErrorInvalidValue;
-    ext_mac_plain_kernel<<<dim3(grid_for(total), a.O), kBlock, 0, s>>>(a, log_n, total);
+    const dim3 grid(grid_for(total), a.O);
+    if (seeded) ext_mac_plain_kernel<MacSeed><<<grid, kBlock, 0, s>>>(core, log_n, total, sd);
+    else ext_mac_plain_kernel<><<<grid, kBlock, 0, s>>>(core, log_n, total);
   }
   return hipGetLastError();
 }
@@ -493,6 +589,10 @@ hipError_t ext_mac_sub(const MacArgs& a, size_t n, size_t sub_degree, hipStream_
   if (a.T == 0 || a.O == 0 || n == 0 || (n & (n - 1))) return hipErrorInvalidValue;
   if (sub_degree == 0 || sub_degree > n || (sub_degree & (sub_degree - 1))) return hipErrorInvalidValue;
   if ((!a.ins && !a.in0) || (!a.pts && !a.pt0) || (!a.outs && !a.out0)) return hipErrorInvalidValue;
+  if (!mac_seed_ok(a)) return hipErrorInvalidValue;
+  const bool seeded = mac_seeded(a);
+  const MacCore& core = a;
+  const MacSeed sd{a.seed_res, a.seed_mult, a.seed_bias};
   const size_t total = static_cast<size_t>(a.Ql + a.P) * n;
   const uint32_t log_n = static_cast<uint32_t>(__builtin_ctzll(n));
   const uint32_t log_g = log_n - static_cast<uint32_t>(__builtin_ctzll(sub_degree));
@@ -506,7 +606,11 @@ hipError_t ext_mac_sub(const MacArgs& a, size_t n, size_t sub_degree, hipStream_
     const dim3 grid(static_cast<unsigned>(tiles * rows));
     const uint32_t r = static_cast<uint32_t>(rows);
     const bool uniform = (size_t(1) << log_g) >= static_cast<size_t>(kMacTile);  // one word per tile
-#define PHX_SUB_LAUNCH(Q, U) ext_mac_sub_tile_kernel<Q, U><<<grid, 64 * kSubWaves, 0, s>>>(a, log_n, log_g, r, total)
+#define PHX_SUB_LAUNCH(Q, U)                                                                                 \
+  do {                                                                                                       \
+    if (seeded) ext_mac_sub_tile_kernel<Q, U, MacSeed><<<grid, 64 * kSubWaves, 0, s>>>(core, log_n, log_g, r, total, sd); \
+    else ext_mac_sub_tile_kernel<Q, U><<<grid, 64 * kSubWaves, 0, s>>>(core, log_n, log_g, r, total);         \
+  } while (0)
     if (a.q60) {
       if (uniform) PHX_SUB_LAUNCH(true, true);
       else PHX_SUB_LAUNCH(true, false);
@@ -517,16 +621,18 @@ hipError_t ext_mac_sub(const MacArgs& a, size_t n, size_t sub_degree, hipStream_
 #undef PHX_SUB_LAUNCH
   } else {
     if (a.O > 65535) return hipErrorInvalidValue;
-    ext_mac_sub_plain_kernel<<<dim3(grid_for(total), a.O), kBlock, 0, s>>>(a, log_n, log_g, total);
+    const dim3 grid(grid_for(total), a.O);
+    if (seeded) ext_mac_sub_plain_kernel<MacSeed><<<grid, kBlock, 0, s>>>(core, log_n, log_g, total, sd);
+    else ext_mac_sub_plain_kernel<><<<grid, kBlock, 0, s>>>(core, log_n, log_g, total);
   }
   return hipGetLastError();
 }
 
 hipError_t conv_weight_slots(const ConvShape& c, const double* dev_W, size_t first_term, size_t count, double* dev_out,
-                             hipStream_t s) {
+                             hipStream_t s, const double* dev_out_scale) {
   if (count == 0) return hipSuccess;
   const size_t ns = c.slots(), total = count * ns;
-  conv_weight_slots_kernel<<<grid_for(total), kBlock, 0, s>>>(c, dev_W, first_term, total,
+  conv_weight_slots_kernel<<<grid_for(total), kBlock, 0, s>>>(c, dev_W, dev_out_scale, first_term, total,
                                                              static_cast<uint32_t>(__builtin_ctzll(ns)),
                                                              reinterpret_cast<double2*>(dev_out));
   return hipGetLastError();

@@ -2,11 +2,13 @@
 #include "conv2d.h"
 
 #include <algorithm>
+#include <cmath>
 #include <complex>
 #include <cstring>
 #include <stdexcept>
 
 #include "../csrc/rns.h"
+#include "numth.h"
 #include "buffer.h"
 #include "encoder.h"
 #include "hip_check.h"
@@ -203,7 +205,8 @@ ConvPlanData::~ConvPlanData() {
 }
 
 std::unique_ptr<ConvPlanData> conv2d_prepare(const PhantomContext& ctx, size_t chain_index, const phx::ConvShape& c,
-                                             const double* dev_W, double pt_scale, int* dev_overflow, hipStream_t s) {
+                                             const double* dev_W, double pt_scale, int* dev_overflow, hipStream_t s,
+                                             const double* out_scale) {
   if (!dev_W) throw std::invalid_argument("null pointer");
   if (!(pt_scale > 0)) throw std::invalid_argument("scale must be positive");
   const phx::MacArgs ma = mac_args(ctx, chain_index);  // checks the chain index and the special primes
@@ -222,10 +225,16 @@ std::unique_ptr<ConvPlanData> conv2d_prepare(const PhantomContext& ctx, size_t c
   PHX_CHECK(hipMalloc(&plan->pts, plan->words * sizeof(uint64_t)));
   // slices of terms that bound the slot vectors' scratch (16 MiB)
   const size_t slice = std::max<size_t>(1, (size_t(1) << 20) / ns);
-  DeviceBuffer<double> slots(std::min(slice, terms) * ns * 2, s);
+  DeviceBuffer<double> slots(std::min(slice, terms) * ns * 2, s), dscale;
+  if (out_scale) {
+    for (size_t h = 0; h < c.out_ch; ++h)
+      if (!std::isfinite(out_scale[h])) throw std::invalid_argument("conv plan: an output scale is not finite");
+    dscale.upload(std::vector<double>(out_scale, out_scale + c.out_ch), s);
+  }
   for (size_t t0 = 0; t0 < terms; t0 += slice) {
     const size_t cnt = std::min(slice, terms - t0);
-    hip_ok(phx::conv_weight_slots(c, dev_W, t0, cnt, slots.get(), s), "conv weight slots");
+    hip_ok(phx::conv_weight_slots(c, dev_W, t0, cnt, slots.get(), s, out_scale ? dscale.get() : nullptr),
+           "conv weight slots");
     encode_sub_raw(ctx, chain_index, true, reinterpret_cast<const std::complex<double>*>(slots.get()), ns, ns, pt_scale,
                    cnt, plan->pts + t0 * QlP * M, dev_overflow, s);
   }
@@ -233,10 +242,73 @@ std::unique_ptr<ConvPlanData> conv2d_prepare(const PhantomContext& ctx, size_t c
   return plan;
 }
 
+std::vector<uint64_t> scaled_constant_residues(double value, double scale, const uint64_t* moduli, size_t count) {
+  if (!moduli) throw std::invalid_argument("null pointer");
+  if (!(scale > 0) || !std::isfinite(scale)) throw std::invalid_argument("scale must be positive and finite");
+  const double x = value * scale;
+  if (!std::isfinite(x)) throw std::invalid_argument("the scaled constant is not finite");
+  int e = 0;
+  const double frac = std::frexp(std::fabs(x), &e);  // |x| = frac 2^e, frac in [1/2, 1)
+  uint64_t mant;
+  int shift = 0;
+  if (e > 53) {  // an integer already: its 53 mantissa bits, times 2^(e - 53)
+    mant = static_cast<uint64_t>(std::ldexp(frac, 53));
+    shift = e - 53;
+  } else {  // below 2^53: the nearest integer, halves away from zero
+    mant = static_cast<uint64_t>(std::llround(std::fabs(x)));
+  }
+  std::vector<uint64_t> r(count);
+  for (size_t i = 0; i < count; ++i) {
+    const uint64_t q = moduli[i];
+    if (q == 0) throw std::invalid_argument("zero modulus");
+    uint64_t v = mant % q;
+    for (int left = shift; left > 0; left -= 60)
+      v = arith::mul_mod(v, (uint64_t(1) << std::min(left, 60)) % q, q);
+    r[i] = (x < 0 && v) ? q - v : v;
+  }
+  return r;
+}
+
+size_t mac_seed_words(size_t O, size_t Ql) { return O + Ql + O * Ql; }
+
+void mac_seed(const PhantomContext& ctx, size_t chain_index, size_t O, const uint64_t* const* res,
+              const uint64_t* res_mult, const uint64_t* bias, uint64_t* table, phx::MacArgs& a, hipStream_t s) {
+  if (!res && !bias) return;
+  if (res && !res_mult) throw std::invalid_argument("a residual needs its multiplier");
+  if (!table) throw std::invalid_argument("null pointer");
+  const RnsTool& rt = ctx.get_context_data(chain_index).gpu_rns_tool();
+  const size_t Ql = rt.size_Ql();
+  const std::vector<uint64_t>& pm = rt.bigP_mod_q_host();
+  const auto& mods = ctx.get_context_data(chain_index).moduli();
+  // [O] residual pointers, [Ql] (m P) mod q_l, [O][Ql] (B_o P) mod q_l
+  std::vector<uint64_t> host(mac_seed_words(O, Ql), 0);
+  if (res) {
+    for (size_t o = 0; o < O; ++o) host[o] = reinterpret_cast<uint64_t>(res[o]);
+    for (size_t l = 0; l < Ql; ++l) host[O + l] = arith::mul_mod(res_mult[l] % mods[l], pm[l], mods[l]);
+  }
+  if (bias)
+    for (size_t o = 0; o < O; ++o)
+      for (size_t l = 0; l < Ql; ++l)
+        host[O + Ql + o * Ql + l] = arith::mul_mod(bias[o * Ql + l] % mods[l], pm[l], mods[l]);
+  for (size_t w0 = 0; w0 < host.size(); w0 += phx::kWordsMax) {
+    const size_t cnt = std::min<size_t>(phx::kWordsMax, host.size() - w0);
+    phx::Words w;
+    std::memcpy(w.w, host.data() + w0, cnt * sizeof(uint64_t));
+    hip_ok(phx::write_words(table + w0, w, cnt, s), "inner-sum seed table");
+  }
+  static_assert(sizeof(uint64_t) == sizeof(const uint64_t*), "pointers are written as words");
+  if (res) {
+    a.seed_res = reinterpret_cast<const uint64_t* const*>(table);
+    a.seed_mult = table + O;
+  }
+  if (bias) a.seed_bias = table + O + Ql;
+}
+
 void conv2d_apply(const PhantomContext& ctx, const ConvPlanData& plan, const uint64_t* const* cts,
                   const uint64_t* const* const* evk, const uint32_t* galois_elts, uint64_t* const* outs,
-                  hipStream_t s) {
+                  hipStream_t s, const uint64_t* const* res, const uint64_t* res_mult, const uint64_t* bias) {
   if (!cts || !evk || !galois_elts || !outs) throw std::invalid_argument("null pointer");
+  if (res && !res_mult) throw std::invalid_argument("conv plan: a residual needs its multiplier");
   if (plan.ctx != &ctx) throw std::invalid_argument("conv plan: prepared for another context");
   const phx::ConvShape& c = plan.shape;
   phx::MacArgs ma = mac_args(ctx, plan.chain_index);
@@ -256,6 +328,11 @@ void conv2d_apply(const PhantomContext& ctx, const ConvPlanData& plan, const uin
   ma.out_stride = ext_words;
   ma.T = static_cast<uint32_t>(T);
   ma.O = c.out_ch;
+  DeviceBuffer<uint64_t> seed;
+  if (res || bias) {
+    seed.allocate(mac_seed_words(c.out_ch, ma.Ql), s);
+    mac_seed(ctx, plan.chain_index, c.out_ch, res, res_mult, bias, seed.get(), ma, s);
+  }
   hip_ok(phx::ext_mac_sub(ma, n, plan.sub_degree, s), "conv inner sums");
   conv_moddown(ctx, plan.chain_index, c, acc.get(), outs, s);
 }

@@ -59,6 +59,7 @@ struct ConvPlanData {
   size_t sub_degree = 0;    // 2 ns
   size_t words = 0;         // of pts
   uint64_t* pts = nullptr;  // [terms][Ql + P][sub_degree], terms ordered (h, k, a, b)
+  std::vector<double> shift;  // b_h of a folded batch norm (DNN::PrepareConvBN), [out_ch]; empty: none
   ConvPlanData() = default;
   ConvPlanData(const ConvPlanData&) = delete;
   ConvPlanData& operator=(const ConvPlanData&) = delete;
@@ -67,14 +68,41 @@ struct ConvPlanData {
 };
 // conv_weight_slots -> encode_sub_raw (ext, ns slots, pt_scale) of every term, in slices that bound
 // the scratch; waits for `s` before returning and never reads dev_W afterwards.  Refuses what
-// conv2d_raw refuses, and 2 ns < 8.
+// conv2d_raw refuses, and 2 ns < 8.  out_scale (host [out_ch], null: all 1.0): the weights of output
+// channel h are multiplied by out_scale[h] in FP64 on the device before they are encoded (a batch
+// norm's a_h folded into the layer); dev_W itself is not modified.
 std::unique_ptr<ConvPlanData> conv2d_prepare(const PhantomContext& ctx, size_t chain_index, const phx::ConvShape& c,
-                                             const double* dev_W, double pt_scale, int* dev_overflow, hipStream_t s);
+                                             const double* dev_W, double pt_scale, int* dev_overflow, hipStream_t s,
+                                             const double* out_scale = nullptr);
 // conv2d_raw with the plan in place of the weights: the modups and batched rotations, one
 // phx::ext_mac_sub launch over all output channels, the batched moddown.  Enqueued in order, nothing
 // synchronised, no encode.  Refuses a plan of another context.
+//
+// Fused affine terms (all optional): res (host [out_ch] of device [2][Ql][n] ciphertexts at the plan's
+// chain index, entries may be null) with res_mult (host [Ql], m mod q_l), and bias (host
+// [out_ch][Ql], B_h mod q_l).  out_h = layer_h + m res_h + (B_h on c0) modulo q_l, word for word what
+// the layer without them returns plus those terms: both enter the one inner-sum launch as its seed,
+// multiplied by P mod q_l here, and a multiple of P passes through the moddown exactly (csrc/conv.h).
+// The seed's tables are written in stream order (phx::write_words); no other launch, no pass over
+// memory and no synchronisation is added.  res without res_mult is refused.
 void conv2d_apply(const PhantomContext& ctx, const ConvPlanData& plan, const uint64_t* const* cts,
                   const uint64_t* const* const* evk, const uint32_t* galois_elts, uint64_t* const* outs,
-                  hipStream_t s);
+                  hipStream_t s, const uint64_t* const* res = nullptr, const uint64_t* res_mult = nullptr,
+                  const uint64_t* bias = nullptr);
+
+// round(value scale) mod q for every q of `moduli`: the constant polynomial of a bias at a scale that
+// may exceed 2^64.  The product is one FP64 value, m 2^e with an integer m below 2^53; for e >= 0 it
+// is that integer exactly and its residue is (m mod q) 2^e mod q (the mantissa-and-power-of-two path
+// of GetElementForEvalAddOrSub, without its cast to 64 bits); below 2^53 it is rounded to the nearest
+// integer, halves away from zero.  A negative product gives q - (|B| mod q).  std::invalid_argument:
+// a product that is not finite, a scale that is not positive, a zero modulus.
+std::vector<uint64_t> scaled_constant_residues(double value, double scale, const uint64_t* moduli, size_t count);
+
+// the seed tables of an inner-sum launch in `table` (device, mac_seed_words(O, Ql) words), written in
+// stream order, and their pointers in `a`: res / res_mult / bias as conv2d_apply takes them, with
+// res_mult and bias multiplied by P mod q_l.  Refuses res without res_mult.
+size_t mac_seed_words(size_t O, size_t Ql);
+void mac_seed(const PhantomContext& ctx, size_t chain_index, size_t O, const uint64_t* const* res,
+              const uint64_t* res_mult, const uint64_t* bias, uint64_t* table, phx::MacArgs& a, hipStream_t s);
 
 }  // namespace phantom

@@ -151,13 +151,51 @@ DNN::ConvPlan DNN::PrepareConv(const double* dev_W, size_t kernel_h, size_t in_c
   return plan;
 }
 
+DNN::ConvPlan DNN::PrepareConvBN(const Weight4& weight, const BNParams& bn, size_t width, size_t slotstr,
+                                 size_t chain_index) {
+  size_t K, in_ch, out_ch;
+  const std::vector<double> w = flatten_weight(weight, K, in_ch, out_ch, "PrepareConvBN");
+  DeviceBuffer<double> dW;
+  dW.upload(w, context_.stream());
+  return PrepareConvBN(dW.get(), K, in_ch, out_ch, bn, width, slotstr, chain_index);
+}
+
+DNN::ConvPlan DNN::PrepareConvBN(const double* dev_W, size_t kernel_h, size_t in_ch, size_t out_ch, const BNParams& bn,
+                                 size_t width, size_t slotstr, size_t chain_index) {
+  if (!dev_W) throw std::invalid_argument("PrepareConvBN: null weights");
+  if (bn.weight.size() != out_ch || bn.bias.size() != out_ch || bn.mean.size() != out_ch || bn.var.size() != out_ch)
+    throw std::invalid_argument("PrepareConvBN: one weight, bias, mean and variance per output channel");
+  const phx::ConvShape shape = conv_shape(context_.poly_degree(), width, slotstr, kernel_h, in_ch, out_ch);
+  const double eps = 1e-5;  // BatchNorm's
+  std::vector<double> a(out_ch), b(out_ch);
+  for (size_t h = 0; h < out_ch; ++h) {
+    a[h] = bn.weight[h] / std::sqrt(bn.var[h] + eps);
+    b[h] = bn.bias[h] - a[h] * bn.mean[h];
+    if (!std::isfinite(a[h]) || !std::isfinite(b[h]))
+      throw std::invalid_argument("PrepareConvBN: a batch-norm parameter is not finite");
+  }
+  hipStream_t s = context_.stream();
+  DeviceBuffer<int> flag(1, s);
+  PHX_CHECK(hipMemsetAsync(flag.get(), 0, sizeof(int), s));
+  ConvPlan plan;
+  plan.data_ = conv2d_prepare(context_, chain_index, shape, dev_W, static_cast<double>(scale_), flag.get(), s, a.data());
+  if (flag.download(s)[0]) throw std::invalid_argument("PrepareConvBN: encoded weights are too large");
+  plan.data_->shift = std::move(b);
+  return plan;
+}
+
 TensorCT DNN::Conv(const TensorCT& input, const ConvPlan& plan, size_t stride) {
   if (!plan) throw std::invalid_argument("Conv: empty plan");
   return conv_run(input, nullptr, plan.data_.get(), plan.kernel(), plan.out_ch(), stride);
 }
 
+TensorCT DNN::ConvAdd(const TensorCT& input, const ConvPlan& plan, const TensorCT& residual, size_t stride) {
+  if (!plan) throw std::invalid_argument("ConvAdd: empty plan");
+  return conv_run(input, nullptr, plan.data_.get(), plan.kernel(), plan.out_ch(), stride, &residual);
+}
+
 TensorCT DNN::conv_run(const TensorCT& input, const double* dev_W, const ConvPlanData* plan, size_t kernel_h,
-                       size_t out_ch, size_t stride) {
+                       size_t out_ch, size_t stride, const TensorCT* residual) {
   if (stride != 1 && stride != 2) throw std::invalid_argument("Conv: stride must be 1 or 2");
   const size_t in_ch = input.num_ch_, n = context_.poly_degree();
   if (in_ch == 0 || input.ctks_.size() != in_ch) throw std::invalid_argument("Conv: channel count mismatch");
@@ -199,6 +237,49 @@ TensorCT DNN::conv_run(const TensorCT& input, const double* dev_W, const ConvPla
   result.width_ = input.width_ / stride;
   result.num_ch_ = out_ch;
   result.slotstr_ = stride == 2 ? input.slotstr_ + 1 : input.slotstr_;
+  const double out_scale = in[0].scale() * static_cast<double>(scale_);
+
+  // the fused affine terms of a prepared layer (host/conv2d.h), checked before the layer is enqueued
+  const size_t Ql = in[0].coeff_modulus_size();
+  const auto& mods = context_.get_context_data(chain).moduli();
+  std::vector<uint64_t> bias, res_mult;
+  std::vector<PhantomCiphertext> res_adj;
+  std::vector<const uint64_t*> res;
+  if (residual) {
+    if (!plan) throw std::invalid_argument("ConvAdd: needs a prepared layer");
+    if (residual->width_ != result.width_ || residual->slotstr_ != result.slotstr_ || residual->num_ch_ != out_ch)
+      throw std::invalid_argument("ConvAdd: the residual's geometry or channel count differs from the output's");
+    check_uniform(*residual, "ConvAdd");
+    const PhantomCiphertext& r0 = residual->ctks_[0];
+    const size_t res_chain = r0.chain_index() + (r0.GetNoiseScaleDeg() == 2 ? 1 : 0);
+    if (r0.GetNoiseScaleDeg() > 2) throw std::invalid_argument("ConvAdd: the residual's noise-scale degree exceeds 2");
+    if (res_chain > chain) throw std::invalid_argument("ConvAdd: the residual is at a later chain index than the layer");
+    if (r0.GetNoiseScaleDeg() == 2 || res_chain < chain) {
+      res_adj = residual->ctks_;
+      for (PhantomCiphertext& c : res_adj) {
+        if (c.GetNoiseScaleDeg() == 2) EvalModReduceInPlace(context_, c, 1);
+        if (c.chain_index() < chain) ModSwitchLevelInPlace(context_, c, chain - c.chain_index());
+      }
+    }
+    const std::vector<PhantomCiphertext>& rc = res_adj.empty() ? residual->ctks_ : res_adj;
+    const double ratio = out_scale / rc[0].scale();
+    if (!(ratio >= 1.5) || !(ratio <= 0x1p62))
+      throw std::invalid_argument("ConvAdd: the output's scale must be 2 to 2^62 times the residual's");
+    const uint64_t m = static_cast<uint64_t>(std::llround(ratio));
+    res_mult.resize(Ql);
+    for (size_t l = 0; l < Ql; ++l) res_mult[l] = m % mods[l];
+    res.resize(out_ch);
+    for (size_t h = 0; h < out_ch; ++h) res[h] = rc[h].data();
+  }
+  if (plan && !plan->shift.empty()) {
+    if (plan->shift.size() != out_ch) throw std::invalid_argument("Conv: the plan's shifts differ from its output channels");
+    bias.resize(out_ch * Ql);
+    for (size_t h = 0; h < out_ch; ++h) {
+      const std::vector<uint64_t> r = scaled_constant_residues(plan->shift[h], out_scale, mods.data(), Ql);
+      std::copy(r.begin(), r.end(), bias.begin() + h * Ql);
+    }
+  }
+
   result.ctks_.resize(out_ch);
   hipStream_t s = context_.stream();
   std::vector<const uint64_t*> cts(in_ch);
@@ -208,14 +289,15 @@ TensorCT DNN::conv_run(const TensorCT& input, const double* dev_W, const ConvPla
     PhantomCiphertext& o = result.ctks_[h];
     o.resize(context_, chain, 2, s, false);
     o.set_ntt_form(true);
-    o.set_scale(in[0].scale() * static_cast<double>(scale_));
+    o.set_scale(out_scale);
     o.SetNoiseScaleDeg(in[0].GetNoiseScaleDeg() + 1);
     o.set_correction_factor(in[0].correction_factor());
     o.set_asymmetric(in[0].is_asymmetric());
     outs[h] = o.data();
   }
   if (plan) {
-    conv2d_apply(context_, *plan, cts.data(), evk.data(), elts.data(), outs.data(), s);
+    conv2d_apply(context_, *plan, cts.data(), evk.data(), elts.data(), outs.data(), s, res.empty() ? nullptr : res.data(),
+                 res_mult.empty() ? nullptr : res_mult.data(), bias.empty() ? nullptr : bias.data());
   } else {
     encoder_.set_sparse_encode(2 * shape.slots());
     conv2d_raw(context_, chain, cts.data(), shape, dev_W, static_cast<double>(scale_), evk.data(), elts.data(), 0,

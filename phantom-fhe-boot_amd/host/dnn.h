@@ -14,6 +14,9 @@
 // and ReluDegTwo are the reference's channel loops; ReluComposite its sequence with the three
 // bootstrap loops going through BootStrap(.., pack).
 //
+// PrepareConvBN / ConvAdd fold the batch norm and the residual add of a residual block into the
+// prepared convolution (one level instead of two; host/conv2d.h "fused affine terms").
+//
 // Not built here: SoftMax, the weight loader and the ResNet driver.
 #pragma once
 
@@ -49,6 +52,12 @@ struct PackedCT {
   size_t slotstr_ = 0;
   size_t num_ch_ = 0;
   size_t pack_ = 1;
+};
+
+// batch-norm parameters, one entry per channel: y = a x + b with a = weight / sqrt(var + 1e-5),
+// b = bias - a mean (DNN::BatchNorm)
+struct BNParams {
+  std::vector<double> weight, bias, mean, var;
 };
 
 class DNN {
@@ -129,6 +138,23 @@ class DNN {
   // rescale).  The result equals Conv(weight) up to the plaintexts' rounding: the compact encoding
   // rounds 2 ns coefficients, the full-size one N.
   TensorCT Conv(const TensorCT& input, const ConvPlan& plan, size_t stride);
+  // A prepared layer with the batch norm behind it folded in: a_h multiplies output channel h's
+  // weights in FP64 before they are encoded, and Conv(plan) adds the constant round(b_h S_out), S_out
+  // the result's scale, to c0 inside the inner sum (host/conv2d.h "fused affine terms").
+  // Conv(PrepareConvBN) therefore stands for BatchNorm(Conv(PrepareConv)) at the input's chain index,
+  // one level above it.  std::invalid_argument: parameter vectors that are not out_ch long.
+  ConvPlan PrepareConvBN(const Weight4& weight, const BNParams& bn, size_t width, size_t slotstr, size_t chain_index);
+  ConvPlan PrepareConvBN(const double* dev_W, size_t kernel_h, size_t in_ch, size_t out_ch, const BNParams& bn,
+                         size_t width, size_t slotstr, size_t chain_index);
+  // Conv(input, plan, stride) + residual in the same launches: the residual enters the inner sum as
+  // m residual_h with the integer m = llround(S_out / S_res), which has the result's scale up to a
+  // relative 1 / (2 m).  The result's metadata is Conv(plan)'s: the input's chain index, degree
+  // input + 1, scale ct.scale * scale_.  The residual's geometry must be the output's (width / stride,
+  // slotstr + (stride == 2), out_ch channels); a degree-2 residual is rescaled first, one at an
+  // earlier chain index than the layer's loses limbs (ModSwitchLevelInPlace).  std::invalid_argument:
+  // what Conv(plan) refuses, another geometry, a residual at a later chain index or with channels at
+  // different levels, degrees or scales, m below 2 or above 2^62.
+  TensorCT ConvAdd(const TensorCT& input, const ConvPlan& plan, const TensorCT& residual, size_t stride);
   // per channel a x + b with a = weight / sqrt(var + 1e-5), b = bias - a mean (src/dnn.cu:454-480)
   TensorCT BatchNorm(const TensorCT& input, const std::vector<double>& weight, const std::vector<double>& bias,
                      const std::vector<double>& mean, const std::vector<double>& var);
@@ -188,9 +214,10 @@ class DNN {
 
  private:
   void check_uniform(const TensorCT& input, const char* who) const;
-  // the layer on dev_W (conv2d_raw), or on `plan` when it is not null (conv2d_apply)
+  // the layer on dev_W (conv2d_raw), or on `plan` when it is not null (conv2d_apply, with the plan's
+  // shift and, when not null, the residual)
   TensorCT conv_run(const TensorCT& input, const double* dev_W, const ConvPlanData* plan, size_t kernel_h, size_t out_ch,
-                    size_t stride);
+                    size_t stride, const TensorCT* residual = nullptr);
   static std::vector<double> flatten_weight(const Weight4& weight, size_t& K, size_t& in_ch, size_t& out_ch,
                                             const char* who);
   // the checks, the rescale of a degree-2 input and the coefficient residues [T][t][L] that

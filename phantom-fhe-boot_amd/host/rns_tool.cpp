@@ -161,6 +161,7 @@ RnsTool::RnsTool(size_t n, const std::vector<uint64_t>& qp, size_t size_P, size_
     pim[i] = inv_mod(P, q);
     pims[i] = shoup(pim[i], q);
   }
+  bigP_mod_q_ = pm;
   d_bigP_mod_q_.upload(pm, s);
   d_bigP_mod_q_shoup_.upload(pms, s);
   d_bigPInv_mod_q_.upload(pim, s);

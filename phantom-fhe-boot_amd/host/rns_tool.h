@@ -104,11 +104,12 @@ class RnsTool {
   phx::ModView mod_QlP() const { return {d_QlP_.get(), d_QlP_barrett_.get()}; }
   const uint64_t* bigP_mod_q() const { return d_bigP_mod_q_.get(); }
   const uint64_t* bigP_mod_q_shoup() const { return d_bigP_mod_q_shoup_.get(); }
+  const std::vector<uint64_t>& bigP_mod_q_host() const { return bigP_mod_q_; }  // the same residues [size_Ql]
 
  private:
   size_t n_, size_Q_, size_P_;
   Workspace* ws_ = nullptr;
-  std::vector<uint64_t> base_Ql_, base_P_;
+  std::vector<uint64_t> base_Ql_, base_P_, bigP_mod_q_;
   DeviceBuffer<uint64_t> d_Ql_, d_Ql_barrett_, d_QlP_, d_QlP_barrett_;
   // key switching
   DeviceBuffer<uint64_t> d_partQlHatInv_, d_partQlHatInv_shoup_;

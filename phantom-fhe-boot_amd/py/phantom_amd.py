@@ -164,6 +164,15 @@ _SIGS = {
     "phantom_conv_plan_destroy": (ctypes.c_int, [vp]),
     "phantom_conv2d_apply": (ctypes.c_int, [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.POINTER(vp)), sz,
                                             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(vp), vp]),
+    "phantom_ext_mac_sub_seeded": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, vp, sz, sz, ctypes.POINTER(vp),
+                                                  ctypes.POINTER(vp), vp, vp, vp]),
+    "phantom_conv2d_prepare_scaled": (ctypes.c_int, [vp, sz, sz, sz, sz, sz, sz, vp, vp, ctypes.c_double, vp, vp,
+                                                     ctypes.POINTER(vp)]),
+    "phantom_conv2d_apply_seeded": (ctypes.c_int, [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.POINTER(vp)), sz,
+                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(vp),
+                                                   ctypes.POINTER(vp), vp, vp, vp]),
+    "phantom_conv_plan_read": (ctypes.c_int, [vp, vp, sz]),
+    "phantom_scaled_constant_residues": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, vp, sz, vp]),
 }
 
 _lib = None
@@ -529,6 +538,30 @@ class Conv:
         return ConvPlan(h, shape)
 
     @staticmethod
+    def prepare_scaled(ctx, chain_index, shape, dev_W, out_scale, pt_scale, stream, overflow=None):
+        """prepare with output channel h's weights multiplied by out_scale[h] (host float64 [out_ch], or
+        None) in FP64 on the device before the encode"""
+        import numpy as np
+        width, slotstr, kernel, in_ch, out_ch = shape
+        sc = None
+        if out_scale is not None:
+            sc = np.ascontiguousarray(out_scale, dtype=np.float64)
+            assert sc.shape == (out_ch,)
+        h = vp()
+        check(load().phantom_conv2d_prepare_scaled(ctx.handle, chain_index, in_ch, out_ch, width, slotstr, kernel, dev_W,
+                                                   sc.ctypes.data if sc is not None else None, pt_scale, overflow,
+                                                   stream, ctypes.byref(h)))
+        return ConvPlan(h, shape)
+
+    @staticmethod
+    def apply_seeded(ctx, plan, cts, key_digits, dnum, galois_elts, outs, res, res_mult, bias, stream):
+        """apply plus m res_h + B_h: res a ctypes array of out_ch device pointers (entries may be NULL) or
+        None, res_mult a uint64 array [Ql] (m mod q_l), bias a uint64 array [out_ch, Ql] or None"""
+        check(load().phantom_conv2d_apply_seeded(ctx.handle, plan.handle, cts, key_digits, dnum, galois_elts, outs, res,
+                                                 res_mult.ctypes.data if res_mult is not None else None,
+                                                 bias.ctypes.data if bias is not None else None, stream))
+
+    @staticmethod
     def apply(ctx, plan, cts, key_digits, dnum, galois_elts, outs, stream):
         """cts / outs: ctypes arrays of device pointers; key_digits: array of K^2 arrays of dnum device
         pointers (NULL at the centre tap); galois_elts: ctypes uint32 array"""
@@ -560,6 +593,13 @@ class ConvPlan:
         b = sz(0)
         check(load().phantom_conv_plan_bytes(self.handle, ctypes.byref(b)))
         return b.value
+
+    def words(self):
+        """the plan's plaintext words [terms][Ql + P][2 ns] on the host (waits for the device)"""
+        import numpy as np
+        out = np.zeros(self.bytes // 8, dtype=np.uint64)
+        check(load().phantom_conv_plan_read(self.handle, out.ctypes.data, out.size))
+        return out
 
     def close(self):
         if self.handle:
