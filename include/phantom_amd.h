@@ -770,6 +770,28 @@ int phantom_ct_pack(const phantom_context *ctx, size_t chain_index, const uint64
 int phantom_ct_split(const phantom_context *ctx, size_t chain_index, const uint64_t *const *a,
                      const uint64_t *const *r, size_t count, uint32_t power, uint64_t *const *even,
                      uint64_t *const *odd, hipStream_t stream);
+/* ---- batched same-key rotations: `count` ciphertexts of one level through ONE Galois key (the
+ * levels of the unpacking tree; "rotate every channel by r" of a tensor).  cts, digits and outs are
+ * host arrays of device pointers, 16-byte aligned; key_digits as phantom_fast_rotation_ext's.  Each
+ * result equals the one-ciphertext entries' bit for bit.  Rejected with an error code before any
+ * launch: a null pointer, a bad chain index, a dnum below beta, a misaligned buffer, any output
+ * overlapping any input or another output, and a count of 0 or above 64 for the kernel entry. */
+/* the key switch alone, one launch with the key read once: outs[k] [2][Ql+P][n] =
+ * phantom_fast_rotation_ext(cts[k], digits[k], key_digits, galois_elt, add_first = 1) for k < count
+ * (1..64); cts[k] [2][Ql][n] (its c0 is read), digits[k] [beta][Ql+P][n] */
+int phantom_keyswitch_rotate_many(const phantom_context *ctx, size_t chain_index, size_t count,
+                                  const uint64_t *const *cts, const uint64_t *const *digits,
+                                  const uint64_t *const *key_digits, size_t dnum, uint32_t galois_elt,
+                                  uint64_t *const *outs, hipStream_t stream);
+/* the whole rotation, outs[k] [2][Ql][n] = moddown(keyswitch_rotate(modup(cts[k] c1))) of cts[k]
+ * [2][Ql][n], for any count >= 0: per chunk of phantom_rotate_fused_batch_chunk ciphertexts one batched
+ * phantom_modup, one phantom_keyswitch_rotate_many and one phantom_moddown_from_ntt over 2 count
+ * polynomials; no synchronisation, scratch from the pool */
+int phantom_rotate_fused_batch(const phantom_context *ctx, size_t chain_index, size_t count,
+                               const uint64_t *const *cts, const uint64_t *const *key_digits, size_t dnum,
+                               uint32_t galois_elt, uint64_t *const *outs, hipStream_t stream);
+/* host only: the ciphertexts of one chunk at chain_index (min(64, scratch cap / scratch of one)) */
+int phantom_rotate_fused_batch_chunk(const phantom_context *ctx, size_t chain_index, size_t *out);
 
 #ifdef __cplusplus
 }

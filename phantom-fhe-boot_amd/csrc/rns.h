@@ -214,6 +214,46 @@ struct KsRotateGroupArgs {
 };
 hipError_t keyswitch_rotate_group(const KsRotateGroupArgs& ga, int mode, size_t n, hipStream_t s);
 
+// keyswitch_rotate (mode 1) of `count` (1..kKsManyMax) ciphertexts by the same rotation (evk, perm)
+// in ONE launch.  The per-ciphertext pointers travel in a device table written in stream order
+// (write_words, conv.h), never in the argument block.  A workgroup owns one (limb, output block of
+// kGaloisBlock indices) and with it one source block: it loads that block's 2 beta key words per
+// element into registers once and loops over the ciphertexts, so the key is read from HBM once per
+// launch by construction (times the slices below), whatever the placement.  When QlP n /
+// kGaloisBlock workgroups cannot fill the device the ciphertext loop is split over gridDim.y
+// (keyswitch_rotate_many_slices).  Each result equals its own keyswitch_rotate, bit for bit.
+// n < kGaloisBlock or beta > 4: `count` keyswitch_rotate launches from the host mirror of the table.
+constexpr int kKsManyMax = 64;
+struct KsManyEntry {
+  const uint64_t* digits = nullptr;  // [beta][QlP][n]
+  const uint64_t* c0 = nullptr;      // [Ql][n] (polynomial 0 of the ciphertext)
+  uint64_t* out = nullptr;           // [2][QlP][n]; must not alias any digits / c0 / other out
+};
+struct KsRotateManyArgs {
+  const KsManyEntry* table = nullptr;    // device array of `count` entries
+  const KsManyEntry* host = nullptr;     // the same entries on the host (the fallback's launches)
+  uint32_t count = 0;
+  const uint64_t* const* evk = nullptr;  // device array of beta pointers to [2][size_QP][n]
+  const uint32_t* perm = nullptr;
+  const uint64_t* qp = nullptr;          // full-chain modulus / Barrett tables (by table row)
+  const uint64_t* qp_barrett = nullptr;
+  const uint64_t* pmod = nullptr;        // P mod q_l, Shoup
+  const uint64_t* pmod_shoup = nullptr;
+  uint32_t ql = 0, qlp = 0, size_q = 0, size_p = 0, beta = 0;
+  uint32_t q60 = 0;  // as KsRotateBatchArgs::q60: approximate-quotient reduction below 2^60, else exact
+};
+hipError_t keyswitch_rotate_many(const KsRotateManyArgs& a, size_t n, hipStream_t s);
+// gridDim.y of that launch: how many slices the ciphertext loop is split into (each reads the key)
+uint32_t keyswitch_rotate_many_slices(uint32_t count, uint32_t qlp, size_t n);
+
+// `count` copies of `words` (even) words each in one launch: pairs[k] = {source, destination}, a
+// device table written in stream order; 16-byte aligned, no overlap
+struct CopyPair {
+  const uint64_t* src = nullptr;
+  uint64_t* dst = nullptr;
+};
+hipError_t copy_many(const CopyPair* pairs, size_t count, size_t words, hipStream_t s);
+
 // Batched baby steps: keyswitch_rotate (mode 1) for several rotations of one ciphertext in ONE
 // launch.  A workgroup owns a SOURCE block (limb l, kGaloisBlock consecutive indices), reads the
 // shared digits and c0 there once from HBM, and for each entry writes the output block that block

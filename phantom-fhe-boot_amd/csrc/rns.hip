@@ -1056,6 +1056,138 @@ __global__ __launch_bounds__(kBlock) void ks_rotate_batch_kernel(KsRotateBatchAr
   }
 }
 
+// keyswitch_rotate_many: ks_rotate_batch_full's split with the roles swapped.  A workgroup owns one
+// (limb l, output block ob) and its source block sb; the block's key words (both halves, every
+// digit) are loaded once, split in 30-bit halves and kept in registers, and the loop runs over the
+// ciphertexts blockIdx.y * per .. of the pointer table.  Ciphertext k + 1's digits and c0 are issued
+// before ciphertext k's barrier and gather, the products go to LDS buffer k & 1 (one barrier per
+// ciphertext, as ks_rotate_batch_full).  The c0 words are loaded on every limb (limb 0's on the
+// special limbs, times a zero constant), so no branch stands between the loads and the barrier.
+// Partial sums as ks_rotate_batch_full's: ll, hh <= 4 (2^31 - 1)^2 and mm <= 8 (2^30 - 1)(2^31 - 1)
+// below 2^64 for moduli up to 61 bits (exact form); below 2^60 ll, hh < 2^62 and mm < 2^63 (FAST).
+// Both reductions return the canonical residue, so the result is ks_rotate_kernel<1>'s.
+template <int BETA, bool FAST>
+__global__ __launch_bounds__(kBlock, BETA <= 2 ? 4 : BETA == 3 ? 3 : 2) void ks_rotate_many_full(KsRotateManyArgs a, uint32_t log_n,
+                                                                                  uint32_t per) {
+  constexpr uint32_t bsz = kGalB;
+  constexpr int PP = kGalB / 2 / kBlock;  // pairs per thread
+  constexpr int GM = bsz / kBlock;        // gathered outputs per thread
+  static_assert(BETA <= 4, "split partial sums");
+  constexpr uint64_t kM30 = (1ull << 30) - 1;
+  __shared__ uint64_t s0[2][kGalB], s1[2][kGalB];
+  static_assert(sizeof(KsManyEntry) == 3 * sizeof(uint64_t), "entries are staged as words");
+  __shared__ uint64_t tab[kKsManyMax][3];  // {digits, c0, out}
+  const uint32_t nb = (1u << log_n) / bsz;
+  const uint32_t l = blockIdx.x / nb, ob = blockIdx.x % nb;
+  const uint32_t first = blockIdx.y * per;
+  const int nk = static_cast<int>(min(a.count - first, per));  // >= 1: gridDim.y = ceil(count / per)
+  if (threadIdx.x < 3 * static_cast<uint32_t>(nk))
+    tab[threadIdx.x / 3][threadIdx.x % 3] = reinterpret_cast<const uint64_t*>(a.table + first)[threadIdx.x];
+  const uint32_t twr = l >= a.ql ? a.size_q + (l - a.ql) : l;
+  const uint64_t q = a.qp[twr], r0 = a.qp_barrett[2 * twr], r1 = a.qp_barrett[2 * twr + 1];
+  const size_t lbase = (size_t)l << log_n, kbase = (size_t)twr << log_n;
+  const size_t qlp_n = (size_t)a.qlp << log_n, qp_n = (size_t)(a.size_q + a.size_p) << log_n;
+  const bool addc = l < a.ql;
+  const uint64_t w = addc ? a.pmod[l] : 0, ws = addc ? a.pmod_shoup[l] : 0;
+  const size_t cbase = addc ? lbase : 0;
+  const SplitRed sr = split_red(q, r0, r1);
+  const __attribute__((address_space(1))) uint32_t* pm =
+      (const __attribute__((address_space(1))) uint32_t*)a.perm + (size_t)ob * bsz;
+  const size_t j0 = pm[0] & ~(bsz - 1);  // the source block
+  uint32_t src[GM];
+#pragma unroll
+  for (int m = 0; m < GM; ++m) src[m] = pm[threadIdx.x + m * kBlock] & (bsz - 1);
+  // the block's keys, once: [pair][digit][key half][element] in 30-bit halves
+  uint32_t kl[PP][BETA][2][2], kh[PP][BETA][2][2];
+#pragma unroll
+  for (int b = 0; b < BETA; ++b) {
+    const uint64_t* key = a.evk[b];
+#pragma unroll
+    for (int p = 0; p < PP; ++p) {
+      const size_t j = j0 + 2 * (threadIdx.x + p * kBlock);
+      const u64x2 k0 = ld2_nt(key + kbase + j), k1 = ld2_nt(key + qp_n + kbase + j);
+      const uint64_t kv[2][2] = {{k0.x, k0.y}, {k1.x, k1.y}};
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          kl[p][b][t][u] = static_cast<uint32_t>(kv[t][u] & kM30);
+          kh[p][b][t][u] = static_cast<uint32_t>(kv[t][u] >> 30);
+        }
+    }
+  }
+  __syncthreads();  // the table
+  u64x2 d[PP][BETA], c0v[PP];
+  auto load_ct = [&](int k) {
+    const uint64_t* dig = uniform_ptr(reinterpret_cast<const uint64_t*>(tab[k][0]));
+    const uint64_t* c0 = uniform_ptr(reinterpret_cast<const uint64_t*>(tab[k][1]));
+#pragma unroll
+    for (int p = 0; p < PP; ++p) {
+      const size_t j = j0 + 2 * (threadIdx.x + p * kBlock);
+#pragma unroll
+      for (int b = 0; b < BETA; ++b) d[p][b] = ld2(dig + b * qlp_n + lbase + j);
+      c0v[p] = ld2(c0 + cbase + j);
+    }
+  };
+  load_ct(0);
+  for (int k = 0; k < nk; ++k) {
+    uint64_t* t0 = s0[k & 1];
+    uint64_t* t1 = s1[k & 1];
+#pragma unroll
+    for (int p = 0; p < PP; ++p) {
+      const uint32_t i = threadIdx.x + p * kBlock;
+      uint64_t ll[2][2] = {{0, 0}, {0, 0}}, mm[2][2] = {{0, 0}, {0, 0}}, hh[2][2] = {{0, 0}, {0, 0}};
+#pragma unroll
+      for (int b = 0; b < BETA; ++b) {
+        const uint64_t dv[2] = {d[p][b].x, d[p][b].y};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const uint32_t dl = static_cast<uint32_t>(dv[u] & kM30), dh = static_cast<uint32_t>(dv[u] >> 30);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            ll[t][u] += static_cast<uint64_t>(dl) * kl[p][b][t][u];
+            mm[t][u] += static_cast<uint64_t>(dl) * kh[p][b][t][u];
+            mm[t][u] += static_cast<uint64_t>(dh) * kl[p][b][t][u];
+            hh[t][u] += static_cast<uint64_t>(dh) * kh[p][b][t][u];
+          }
+        }
+      }
+      auto red = [&](uint64_t x, uint64_t y, uint64_t z) {
+        if constexpr (FAST && PHX_KS_RED == 2) return split_reduce2(x, y, z, sr, q, r1);
+        else if constexpr (FAST) return split_reduce(x, y, z, sr, q, r1);
+        else return split_reduce_exact(x, y, z, sr, q, r1);
+      };
+      t0[2 * i] = add_mod(red(ll[0][0], mm[0][0], hh[0][0]), mul_shoup(c0v[p].x, w, ws, q), q);
+      t0[2 * i + 1] = add_mod(red(ll[0][1], mm[0][1], hh[0][1]), mul_shoup(c0v[p].y, w, ws, q), q);
+      t1[2 * i] = red(ll[1][0], mm[1][0], hh[1][0]);
+      t1[2 * i + 1] = red(ll[1][1], mm[1][1], hh[1][1]);
+    }
+    // the next ciphertext's digits and c0 (the last one's again at the end: cache hits) in flight
+    // over the barrier and the gather
+    __builtin_amdgcn_sched_barrier(0);
+    load_ct(min(k + 1, nk - 1));
+    ks_lt_barrier();
+    // (a pointer read from LDS: the explicit address space keeps the stores global, not flat)
+    using GU64 = __attribute__((address_space(1))) uint64_t;
+    GU64* out = (GU64*)(uniform_ptr(reinterpret_cast<uint64_t*>(tab[k][2])) + lbase + (size_t)ob * bsz);
+#pragma unroll
+    for (int m = 0; m < GM; ++m) {
+      const uint32_t i = threadIdx.x + m * kBlock;
+      out[i] = t0[src[m]];
+      out[qlp_n + i] = t1[src[m]];
+    }
+  }
+}
+
+// pairs[blockIdx.y]: dst = src, `words` words (even), 16 bytes per lane
+__global__ __launch_bounds__(kBlock) void copy_many_kernel(const CopyPair* pairs, size_t words) {
+  const CopyPair c = pairs[blockIdx.y];
+  for (size_t i = 2 * ((size_t)blockIdx.x * kBlock + threadIdx.x); i < words; i += 2 * (size_t)gridDim.x * kBlock) {
+    const u64x2 v = ld2(c.src + i);
+    st2(c.dst + i, v.x, v.y);
+  }
+}
+
 // keyswitch_rotate_sum: workgroup = (limb l, OUTPUT block ob).  Entry k's source block differs from
 // entry to entry, so its digits and c0 are loaded with its keys; the products go to LDS buffer k & 1
 // (one barrier per entry, as ks_rotate_batch_full) and are gathered into per-thread running sums
@@ -1573,6 +1705,63 @@ hipError_t keyswitch_rotate_group(const KsRotateGroupArgs& ga, int mode, size_t 
     case 1: ks_rotate_kernel<1, true><<<grid, kBlock, 0, s>>>(ga, log_n, bsz); break;
     default: ks_rotate_kernel<2, true><<<grid, kBlock, 0, s>>>(ga, log_n, bsz); break;
   }
+  return hipGetLastError();
+}
+
+uint32_t keyswitch_rotate_many_slices(uint32_t count, uint32_t qlp, size_t n) {
+  if (count == 0 || qlp == 0 || n < kGalB) return 1;
+  // two workgroups per CU are wanted before a slice reads the key a second time
+  const uint64_t blocks = static_cast<uint64_t>(qlp) * (n / kGalB), want = 2 * static_cast<uint64_t>(num_cus());
+  const uint64_t slices = std::min<uint64_t>(count, std::max<uint64_t>(1, (want + blocks - 1) / blocks));
+  const uint32_t per = static_cast<uint32_t>((count + slices - 1) / slices);
+  return (count + per - 1) / per;
+}
+
+hipError_t keyswitch_rotate_many(const KsRotateManyArgs& a, size_t n, hipStream_t s) {
+  if (!a.table || !a.host || !a.evk || !a.perm || !a.qp || !a.qp_barrett || !a.pmod || !a.pmod_shoup || a.beta == 0 ||
+      a.ql == 0 || a.ql > a.qlp || a.count < 1 || a.count > static_cast<uint32_t>(kKsManyMax) || n < 2 || (n & (n - 1)))
+    return hipErrorInvalidValue;
+  for (uint32_t k = 0; k < a.count; ++k)
+    if (!a.host[k].digits || !a.host[k].c0 || !a.host[k].out) return hipErrorInvalidValue;
+  if (n < kGalB || a.beta > 4) {  // the shapes without the register-resident form: one launch each
+    for (uint32_t k = 0; k < a.count; ++k) {
+      KsRotateArgs g;
+      g.digits = a.host[k].digits;
+      g.evk = a.evk;
+      g.qp = a.qp;
+      g.qp_barrett = a.qp_barrett;
+      g.c0 = a.host[k].c0;
+      g.pmod = a.pmod;
+      g.pmod_shoup = a.pmod_shoup;
+      g.out = a.host[k].out;
+      g.perm = a.perm;
+      g.ql = a.ql, g.qlp = a.qlp, g.size_q = a.size_q, g.size_p = a.size_p, g.beta = a.beta;
+      if (hipError_t e = keyswitch_rotate(g, 1, n, s)) return e;
+    }
+    return hipSuccess;
+  }
+  const uint32_t log_n = __builtin_ctzll(n);
+  const uint32_t slices = keyswitch_rotate_many_slices(a.count, a.qlp, n), per = (a.count + slices - 1) / slices;
+  const dim3 grid(static_cast<uint32_t>(a.qlp * (n / kGalB)), (a.count + per - 1) / per);
+#define PHX_KSMANY(B)                                                                  \
+  case B:                                                                              \
+    if (a.q60) ks_rotate_many_full<B, true><<<grid, kBlock, 0, s>>>(a, log_n, per);    \
+    else ks_rotate_many_full<B, false><<<grid, kBlock, 0, s>>>(a, log_n, per);         \
+    break;
+  switch (a.beta) {
+    PHX_KSMANY(1) PHX_KSMANY(2) PHX_KSMANY(3)
+    default:
+    PHX_KSMANY(4)
+  }
+#undef PHX_KSMANY
+  return hipGetLastError();
+}
+
+hipError_t copy_many(const CopyPair* pairs, size_t count, size_t words, hipStream_t s) {
+  if (!pairs || (words & 1) || count > 65535) return hipErrorInvalidValue;
+  if (count == 0 || words == 0) return hipSuccess;
+  const dim3 grid = poly_grid(words / 2, count);
+  copy_many_kernel<<<grid, kBlock, 0, s>>>(pairs, words);
   return hipGetLastError();
 }
 

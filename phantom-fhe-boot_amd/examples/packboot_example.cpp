@@ -26,6 +26,15 @@
 //          2 (64 x width 8, slotstr 2); side = both | pack1 | packed (separate invocations hold one
 //          bootstrap setup each); what = boot | relu | all.  Device time from events on the context's
 //          stream, median and range of `reps` (default 5) runs after a warm-up, and the maximum error.
+//        packboot_example check tree [log_n]
+//          EvalRotateFusedBatch against EvalRotateFused word for word (counts 1, 5 and the chunk size
+//          + 1, inputs of different scales in one call, once with the unbiased moddown on),
+//          unpack_channels_batch against unpack_channels word for word per case (and two full groups),
+//          and the refusals of EvalRotateFusedBatch.
+//        packboot_example tree <stage> [reps]
+//          log_n = 16, the three stages above, the packed groups at the bootstrap's output level (12
+//          limbs): device time of Unpack through unpack_channels (one EvalRotateFused per node) and
+//          through unpack_channels_batch (one batched rotation per level), both in this process.
 // One JSON line per case and a last `done` line; exit status 0 iff every line is ok.
 #include <hip/hip_runtime.h>
 
@@ -447,6 +456,132 @@ static int run_check_relu(int log_n) {
   return all ? 0 : 1;
 }
 
+// ---- check tree ---------------------------------------------------------------------------------
+
+static bool rotate_batch_case(Rig& r, const char* name, const std::vector<PhantomCiphertext>& in, int index) {
+  const PhantomContext& ctx = r.ctx;
+  std::vector<const PhantomCiphertext*> ptrs;
+  for (const PhantomCiphertext& c : in) ptrs.push_back(&c);
+  const std::vector<PhantomCiphertext> got = EvalRotateFusedBatch(ctx, ptrs, r.model.galois_keys(), index);
+  bool equal = got.size() == in.size();
+  for (size_t k = 0; equal && k < in.size(); ++k)
+    equal = same_ct(ctx, got[k], EvalRotateFused(ctx, in[k], r.model.galois_keys(), index));
+  std::printf("{\"check\": \"%s\", \"log_n\": %zu, \"count\": %zu, \"chunk\": %zu, \"limbs\": %zu, \"rotation\": %d, "
+              "\"unbiased_moddown\": %s, \"rotate_words_equal\": %s, \"ok\": %s}\n",
+              name, log2_of(r.n), in.size(), rotate_fused_batch_chunk(ctx, in[0].chain_index()),
+              in[0].coeff_modulus_size(), index, tf(ctx.unbiased_moddown()), tf(equal), tf(equal));
+  std::fflush(stdout);
+  return equal;
+}
+
+static bool tree_case(Rig& r, const Case& c, uint64_t seed) {
+  const PhantomContext& ctx = r.ctx;
+  std::mt19937_64 rng(seed);
+  const TensorCT input = r.model.EncTensor(random_image(c.width, c.C, rng, false), r.pk, c.slotstr);
+  const PackPlan plan = pack_plan(r.n, c.width, c.slotstr, c.P);
+  const PackedCT packed = r.model.Pack(input, c.P);
+  std::vector<const PhantomCiphertext*> groups;
+  std::vector<size_t> members;
+  for (size_t g = 0; g < packed.ctks_.size(); ++g) {
+    groups.push_back(&packed.ctks_[g]);
+    members.push_back(plan.members(c.C, g));
+  }
+  const auto got = unpack_channels_batch(ctx, plan, groups, members, r.model.galois_keys());
+  bool equal = got.size() == groups.size();
+  for (size_t g = 0; equal && g < groups.size(); ++g) {
+    const auto want = unpack_channels(ctx, plan, packed.ctks_[g], members[g], r.model.galois_keys());
+    equal = want.size() == got[g].size();
+    for (size_t k = 0; equal && k < want.size(); ++k) equal = same_ct(ctx, got[g][k], want[k]);
+  }
+  // the layer through either path
+  r.model.set_unpack_path(DNN::UnpackPath::kPerNode);
+  const TensorCT per_node = r.model.Unpack(packed);
+  r.model.set_unpack_path(DNN::UnpackPath::kBatched);
+  const bool layer_equal = same_tensor(ctx, r.model.Unpack(packed), per_node);
+  const bool ok = equal && layer_equal;
+  std::printf("{\"check\": \"tree_%s\", \"log_n\": %zu, \"width\": %zu, \"slotstr\": %zu, \"channels\": %zu, \"pack\": %zu, "
+              "\"groups\": %zu, \"tree_words_equal\": %s, \"unpack_words_equal\": %s, \"ok\": %s}\n",
+              c.name, log2_of(r.n), c.width, c.slotstr, c.C, c.P, groups.size(), tf(equal), tf(layer_equal), tf(ok));
+  std::fflush(stdout);
+  return ok;
+}
+
+template <class F>
+static bool refusal(const char* what, F&& f) {
+  bool thrown = false;
+  try {
+    f();
+  } catch (const std::invalid_argument&) {
+    thrown = true;
+  }
+  std::printf("{\"check\": \"refusal\", \"case\": \"%s\", \"thrown\": %s, \"ok\": %s}\n", what, tf(thrown), tf(thrown));
+  std::fflush(stdout);
+  return thrown;
+}
+
+static int run_check_tree(int log_n) {
+  Rig r(log_n);
+  model_keys(r);
+  const PhantomContext& ctx = r.ctx;
+  const PhantomGaloisKey& keys = r.model.galois_keys();
+  bool all = true;
+  std::mt19937_64 rng(0x7EE0);
+  const int index = pack_rotations(8, 0, 4)[0];
+  // ciphertexts at one level, every second one with another scale in its metadata
+  auto inputs = [&](size_t count, size_t limbs) {
+    const TensorCT t = r.model.EncTensor(random_image(8, count, rng, false), r.pk, 0);
+    std::vector<PhantomCiphertext> v = t.ctks_;
+    for (size_t k = 0; k < v.size(); ++k) {
+      if (limbs < v[k].coeff_modulus_size()) ModSwitchLevelInPlace(ctx, v[k], v[k].coeff_modulus_size() - limbs);
+      if (k & 1) v[k].set_scale(v[k].scale() * 3.0);
+    }
+    return v;
+  };
+  all = rotate_batch_case(r, "rotate_batch_1", inputs(1, 30), index) && all;
+  all = rotate_batch_case(r, "rotate_batch_5", inputs(5, 30), index) && all;
+  {
+    const std::vector<PhantomCiphertext> v = inputs(5, 12);
+    const size_t chunk = rotate_fused_batch_chunk(ctx, v[0].chain_index());
+    std::vector<PhantomCiphertext> many;
+    for (size_t k = 0; k < chunk + 1; ++k) many.push_back(v[k % v.size()]);
+    all = rotate_batch_case(r, "rotate_batch_chunk_plus_1", many, index) && all;
+  }
+  r.ctx.set_unbiased_moddown(true);
+  all = rotate_batch_case(r, "rotate_batch_unbiased", inputs(5, 12), index) && all;
+  r.ctx.set_unbiased_moddown(false);
+
+  uint64_t seed = 0x7EE40;
+  for (const Case& c : kCases) all = tree_case(r, c, ++seed) && all;
+  all = tree_case(r, Case{"w8_c8_p4", 8, 0, 8, 4}, ++seed) && all;
+
+  {  // the refusals: nothing may be enqueued, so each is followed by a comparison that still holds
+    const std::vector<PhantomCiphertext> v = inputs(3, 12);
+    PhantomCiphertext lower = v[1];
+    ModSwitchLevelInPlace(ctx, lower, 1);
+    PhantomCiphertext coeff = v[1];
+    coeff.set_ntt_form(false);
+    PhantomCiphertext three = v[1];
+    three.resize(ctx, v[1].chain_index(), 3, ctx.stream(), false);
+    int missing = 1;
+    while (keys.has(FindAutomorphismIndex2nComplex(missing, r.n))) ++missing;
+    auto call = [&](const PhantomCiphertext* a, const PhantomCiphertext* b, int idx) {
+      const PhantomCiphertext* p[3] = {&v[0], a, b};
+      EvalRotateFusedBatch(ctx, p, keys, idx);
+    };
+    all = refusal("different chain indices", [&] { call(&lower, &v[2], index); }) && all;
+    all = refusal("not NTT form", [&] { call(&coeff, &v[2], index); }) && all;
+    all = refusal("three polynomials", [&] { call(&three, &v[2], index); }) && all;
+    all = refusal("null entry", [&] { call(nullptr, &v[2], index); }) && all;
+    all = refusal("missing key", [&] { call(&v[1], &v[2], missing); }) && all;
+    const bool empty = EvalRotateFusedBatch(ctx, {}, keys, index).empty();
+    std::printf("{\"check\": \"empty_span\", \"empty_result\": %s, \"ok\": %s}\n", tf(empty), tf(empty));
+    all = all && empty;
+    all = rotate_batch_case(r, "rotate_batch_after_refusals", v, index) && all;
+  }
+  std::printf("{\"done\": \"packboot_example check tree\", \"ok\": %s}\n", tf(all));
+  return all ? 0 : 1;
+}
+
 // ---- bench --------------------------------------------------------------------------------------
 
 struct Stat {
@@ -535,6 +670,61 @@ static int run_bench(int stage, const std::string& side, int reps, const std::st
   return all ? 0 : 1;
 }
 
+// Unpack alone, per node against batched, on packed groups at the bootstrap's output level
+static int run_tree(int stage, int reps) {
+  static const Case stages[] = {{"stage0", 32, 0, 16, 16}, {"stage1", 16, 1, 32, 32}, {"stage2", 8, 2, 64, 32}};
+  if (stage < 0 || stage > 2 || reps < 1) throw std::invalid_argument("tree <stage 0..2> [reps]");
+  const Case& c = stages[stage];
+  const int log_n = 16;
+  const size_t limbs = 12;  // what EvalBootstrap returns on this chain
+  Rig r(log_n);
+  const PackPlan plan = pack_plan(r.n, c.width, c.slotstr, c.P);
+  std::vector<int32_t> rots;
+  r.model.AddPackRotationsTo(rots, c.width, c.slotstr, c.P);
+  r.model.BuildGaloisKey(r.sk, rots);
+  std::mt19937_64 rng(0x7EE5);
+  TensorCT input = r.model.EncTensor(random_image(c.width, c.C, rng, true), r.pk, c.slotstr);
+  drop_to_limbs(r, input, limbs);
+  const PackedCT packed = r.model.Pack(input, c.P);
+  PHX_CHECK(hipDeviceSynchronize());
+
+  hipStream_t s = r.ctx.stream();
+  hipEvent_t e0, e1;
+  PHX_CHECK(hipEventCreate(&e0));
+  PHX_CHECK(hipEventCreate(&e1));
+  TensorCT out[2];
+  Stat t[2];
+  const DNN::UnpackPath paths[2] = {DNN::UnpackPath::kPerNode, DNN::UnpackPath::kBatched};
+  for (int side = 0; side < 2; ++side) {
+    r.model.set_unpack_path(paths[side]);
+    std::vector<double> ms;
+    for (int i = 0; i <= reps; ++i) {  // run 0 warms up
+      PHX_CHECK(hipStreamSynchronize(s));
+      PHX_CHECK(hipEventRecord(e0, s));
+      out[side] = r.model.Unpack(packed);
+      PHX_CHECK(hipEventRecord(e1, s));
+      PHX_CHECK(hipEventSynchronize(e1));
+      float v = 0;
+      PHX_CHECK(hipEventElapsedTime(&v, e0, e1));
+      if (i) ms.push_back(v);
+    }
+    t[side] = stat(ms);
+  }
+  PHX_CHECK(hipEventDestroy(e0));
+  PHX_CHECK(hipEventDestroy(e1));
+  const bool equal = same_tensor(r.ctx, out[0], out[1]);
+  const size_t groups = plan.groups(c.C);
+  std::printf("{\"bench\": \"Unpack\", \"stage\": %d, \"log_n\": %d, \"channels\": %zu, \"width\": %zu, \"slotstr\": %zu, "
+              "\"pack\": %zu, \"groups\": %zu, \"limbs\": %zu, \"chunk\": %zu, \"tree_rotations\": %zu, \"levels\": %zu, "
+              "\"reps\": %d, \"per_node_ms\": {\"median\": %.3f, \"min\": %.3f, \"max\": %.3f}, "
+              "\"batched_ms\": {\"median\": %.3f, \"min\": %.3f, \"max\": %.3f}, \"words_equal\": %s}\n",
+              stage, log_n, c.C, c.width, c.slotstr, c.P, groups, limbs,
+              rotate_fused_batch_chunk(r.ctx, packed.ctks_[0].chain_index()), groups * (c.P - 1), plan.log_pack, reps,
+              t[0].median, t[0].min, t[0].max, t[1].median, t[1].min, t[1].max, tf(equal));
+  std::printf("{\"done\": \"packboot_example tree\", \"ok\": %s}\n", tf(equal));
+  return equal ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   try {
     if (argc >= 3 && !std::strcmp(argv[1], "check")) {
@@ -543,12 +733,14 @@ int main(int argc, char** argv) {
       if (!std::strcmp(argv[2], "pack")) return run_check_pack(log_n);
       if (!std::strcmp(argv[2], "boot")) return run_check_boot(log_n);
       if (!std::strcmp(argv[2], "relu")) return run_check_relu(log_n);
+      if (!std::strcmp(argv[2], "tree")) return run_check_tree(log_n);
     }
+    if (argc >= 3 && !std::strcmp(argv[1], "tree")) return run_tree(std::atoi(argv[2]), argc >= 4 ? std::atoi(argv[3]) : 5);
     if (argc >= 3 && !std::strcmp(argv[1], "bench"))
       return run_bench(std::atoi(argv[2]), argc >= 4 ? argv[3] : "both", argc >= 5 ? std::atoi(argv[4]) : 5,
                        argc >= 6 ? argv[5] : "all");
-    std::fprintf(stderr, "usage: packboot_example check pack|boot|relu [log_n] | bench <stage> [both|pack1|packed] [reps] "
-                         "[boot|relu|all]\n");
+    std::fprintf(stderr, "usage: packboot_example check pack|boot|relu|tree [log_n] | bench <stage> [both|pack1|packed] [reps] "
+                         "[boot|relu|all] | tree <stage> [reps]\n");
     return 2;
   } catch (const std::exception& e) {
     std::printf("{\"error\": \"%s\", \"ok\": false}\n", e.what());

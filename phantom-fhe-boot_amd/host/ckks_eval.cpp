@@ -1,11 +1,14 @@
 #include "ckks_eval.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <stdexcept>
 
 #include "../csrc/ckks.h"
+#include "../csrc/conv.h"
 #include "../csrc/ntt.h"
 #include "../csrc/rns.h"
 #include "evaluate.h"
@@ -848,6 +851,218 @@ PhantomCiphertext EvalConjFused(const PhantomContext& ctx, const PhantomCipherte
   PhantomCiphertext e =
       EvalFastAutomorphismExt(ctx, ct, keys, static_cast<uint32_t>(2 * ctx.poly_degree() - 1), d.get(), true);
   return KeySwitchDown(ctx, e);
+}
+
+// ---- batched same-key rotations -----------------------------------------------------------
+
+namespace {
+
+const RnsTool& batch_tool(const PhantomContext& ctx, size_t chain_index) {
+  if (chain_index < 1 || chain_index >= ctx.total_parm_size()) throw std::invalid_argument("invalid chain index");
+  return ctx.get_context_data(chain_index).gpu_rns_tool();
+}
+
+bool ranges_meet(const uint64_t* x, size_t xw, const uint64_t* y, size_t yw) { return x < y + yw && y < x + xw; }
+bool misaligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) & 15; }
+
+// host words to device memory in stream order, without a host-to-device copy (phx::write_words)
+void write_table_words(uint64_t* dst, const uint64_t* w, size_t count, hipStream_t s) {
+  for (size_t at = 0; at < count; at += phx::kWordsMax) {
+    const size_t c = std::min<size_t>(phx::kWordsMax, count - at);
+    phx::Words chunk;
+    std::memcpy(chunk.w, w + at, c * sizeof(uint64_t));
+    hip_ok(phx::write_words(dst + at, chunk, c, s), "rotation batch table");
+  }
+}
+
+// `count` copies of `words` words in one launch
+void copy_table(const std::vector<phx::CopyPair>& pairs, size_t words, hipStream_t s) {
+  static_assert(sizeof(phx::CopyPair) == 2 * sizeof(uint64_t), "pairs are written as words");
+  DeviceBuffer<uint64_t> table(2 * pairs.size(), s);
+  write_table_words(table.get(), reinterpret_cast<const uint64_t*>(pairs.data()), 2 * pairs.size(), s);
+  hip_ok(phx::copy_many(reinterpret_cast<const phx::CopyPair*>(table.get()), pairs.size(), words, s), "copy_many");
+}
+
+// words of scratch one ciphertext of a batch takes: the staged c1 and the modup's INTT (Ql each),
+// the digits (beta QlP), the extended result (2 QlP), the moddown's delta and the output slab (2 Ql each)
+size_t batch_words_per_ct(const PhantomContext& ctx, const RnsTool& rt) {
+  const size_t Ql = rt.size_Ql(), QlP = Ql + ctx.size_P();
+  return (6 * Ql + (rt.beta() + 2) * QlP) * ctx.poly_degree();
+}
+
+// one chunk (count <= the chunk size): three stages, results in slab [count][2][Ql][n]
+void rotate_chunk(const PhantomContext& ctx, size_t chain_index, const RnsTool& rt, const uint64_t* const* cts,
+                  size_t count, const uint64_t* const* evk, uint32_t elt, uint64_t* slab, hipStream_t s) {
+  const size_t n = ctx.poly_degree(), Ql = rt.size_Ql(), QlP = Ql + ctx.size_P(), beta = rt.beta();
+  // stage the c1 polynomials side by side (the batched modup takes one stride)
+  DeviceBuffer<uint64_t> c1(count * Ql * n, s), digits(count * beta * QlP * n, s), ext(count * 2 * QlP * n, s);
+  std::vector<phx::CopyPair> pairs(count);
+  for (size_t k = 0; k < count; ++k) pairs[k] = {cts[k] + Ql * n, c1.get() + k * Ql * n};
+  copy_table(pairs, Ql * n, s);
+  rt.modup(digits.get(), c1.get(), ctx.gpu_rns_tables(), s, count, Ql * n);
+  std::vector<const uint64_t*> dg(count);
+  std::vector<uint64_t*> ex(count);
+  for (size_t k = 0; k < count; ++k) {
+    dg[k] = digits.get() + k * beta * QlP * n;
+    ex[k] = ext.get() + k * 2 * QlP * n;
+  }
+  keyswitch_rotate_many_raw(ctx, chain_index, count, cts, dg.data(), evk, elt, ex.data(), s);
+  rt.moddown_add(slab, ext.get(), false, ctx.gpu_rns_tables(), s, 2 * count);
+  traffic::ciphertexts(traffic::limb_bytes(count * (3 * Ql + 4 * QlP + 2 * Ql), n));
+}
+
+void check_batch_inputs(const uint64_t* const* cts, size_t count) {
+  if (!cts) throw std::invalid_argument("rotation batch: null pointer");
+  for (size_t k = 0; k < count; ++k) {
+    if (!cts[k]) throw std::invalid_argument("rotation batch: null ciphertext");
+    if (misaligned16(cts[k])) throw std::invalid_argument("rotation batch: ciphertexts must be 16-byte aligned");
+  }
+}
+
+}  // namespace
+
+size_t rotate_fused_batch_chunk(const PhantomContext& ctx, size_t chain_index) {
+  const RnsTool& rt = batch_tool(ctx, chain_index);
+  const size_t bytes = batch_words_per_ct(ctx, rt) * sizeof(uint64_t);
+  return std::max<size_t>(1, std::min<size_t>(phx::kKsManyMax, kRotateBatchScratchBytes / bytes));
+}
+
+void keyswitch_rotate_many_raw(const PhantomContext& ctx, size_t chain_index, size_t count, const uint64_t* const* cts,
+                               const uint64_t* const* digits, const uint64_t* const* evk, uint32_t galois_elt,
+                               uint64_t* const* outs, hipStream_t s) {
+  const RnsTool& rt = batch_tool(ctx, chain_index);
+  if (!cts || !digits || !evk || !outs) throw std::invalid_argument("keyswitch_rotate_many: null pointer");
+  if (count < 1 || count > static_cast<size_t>(phx::kKsManyMax))
+    throw std::invalid_argument("keyswitch_rotate_many: 1 to 64 ciphertexts");
+  const size_t n = ctx.poly_degree(), Ql = rt.size_Ql(), QlP = Ql + ctx.size_P(), beta = rt.beta();
+  static_assert(sizeof(phx::KsManyEntry) == 3 * sizeof(uint64_t), "entries are written as words");
+  std::vector<phx::KsManyEntry> e(count);
+  for (size_t k = 0; k < count; ++k) {
+    if (!cts[k] || !digits[k] || !outs[k]) throw std::invalid_argument("keyswitch_rotate_many: null pointer");
+    if (misaligned16(cts[k]) || misaligned16(digits[k]) || misaligned16(outs[k]))
+      throw std::invalid_argument("keyswitch_rotate_many: buffers must be 16-byte aligned");
+    e[k].digits = digits[k];
+    e[k].c0 = cts[k];
+    e[k].out = outs[k];
+  }
+  for (size_t k = 0; k < count; ++k) {
+    for (size_t j = 0; j < count; ++j) {
+      if (ranges_meet(outs[k], 2 * QlP * n, cts[j], 2 * Ql * n) || ranges_meet(outs[k], 2 * QlP * n, digits[j], beta * QlP * n))
+        throw std::invalid_argument("keyswitch_rotate_many: an output overlaps an input");
+      if (j > k && ranges_meet(outs[k], 2 * QlP * n, outs[j], 2 * QlP * n))
+        throw std::invalid_argument("keyswitch_rotate_many: two outputs overlap");
+    }
+  }
+  const uint32_t* perm = ctx.galois_perm(galois_elt);
+  DeviceBuffer<uint64_t> table(3 * count, s);
+  write_table_words(table.get(), reinterpret_cast<const uint64_t*>(e.data()), 3 * count, s);
+  phx::KsRotateManyArgs a;
+  a.table = reinterpret_cast<const phx::KsManyEntry*>(table.get());
+  a.host = e.data();
+  a.count = static_cast<uint32_t>(count);
+  a.evk = evk;
+  a.perm = perm;
+  a.qp = ctx.mod_QP().q;
+  a.qp_barrett = ctx.mod_QP().barrett;
+  a.pmod = rt.bigP_mod_q();
+  a.pmod_shoup = rt.bigP_mod_q_shoup();
+  a.ql = static_cast<uint32_t>(Ql);
+  a.qlp = static_cast<uint32_t>(QlP);
+  a.size_q = static_cast<uint32_t>(ctx.size_Q());
+  a.size_p = static_cast<uint32_t>(ctx.size_P());
+  a.beta = static_cast<uint32_t>(beta);
+  a.q60 = below_2_60(ctx.key_moduli());
+  hip_ok(phx::keyswitch_rotate_many(a, n, s), "batched key switch + permute");
+  // the key once per slice; per ciphertext the digits and c0 read, the extended result written
+  traffic::keys(traffic::limb_bytes(phx::keyswitch_rotate_many_slices(a.count, a.qlp, n) * beta * 2 * QlP, n));
+  traffic::ciphertexts(traffic::limb_bytes(count * 2 * QlP, n));
+}
+
+void rotate_fused_batch_slab(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, size_t count,
+                             const uint64_t* const* evk, uint32_t galois_elt, uint64_t* slab, hipStream_t s) {
+  const RnsTool& rt = batch_tool(ctx, chain_index);
+  if (count == 0) return;
+  if (!evk || !slab) throw std::invalid_argument("rotation batch: null pointer");
+  if (count > rotate_fused_batch_chunk(ctx, chain_index)) throw std::invalid_argument("rotation batch: above the chunk size");
+  check_batch_inputs(cts, count);
+  if (misaligned16(slab)) throw std::invalid_argument("rotation batch: ciphertexts must be 16-byte aligned");
+  const size_t words = 2 * rt.size_Ql() * ctx.poly_degree();
+  for (size_t k = 0; k < count; ++k)
+    if (ranges_meet(slab, count * words, cts[k], words)) throw std::invalid_argument("rotation batch: the output overlaps an input");
+  rotate_chunk(ctx, chain_index, rt, cts, count, evk, galois_elt, slab, s);
+}
+
+void rotate_fused_batch_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, size_t count,
+                            const uint64_t* const* evk, uint32_t galois_elt, uint64_t* const* outs, hipStream_t s) {
+  const RnsTool& rt = batch_tool(ctx, chain_index);
+  if (count == 0) return;
+  if (!evk || !outs) throw std::invalid_argument("rotation batch: null pointer");
+  check_batch_inputs(cts, count);
+  const size_t words = 2 * rt.size_Ql() * ctx.poly_degree();
+  for (size_t k = 0; k < count; ++k) {
+    if (!outs[k]) throw std::invalid_argument("rotation batch: null output");
+    if (misaligned16(outs[k])) throw std::invalid_argument("rotation batch: ciphertexts must be 16-byte aligned");
+  }
+  // sorted by address, a buffer can only meet the ones that start within its length after it; two
+  // inputs may coincide
+  std::vector<std::pair<const uint64_t*, bool>> all;  // (buffer, is an output)
+  for (size_t k = 0; k < count; ++k) all.emplace_back(cts[k], false), all.emplace_back(outs[k], true);
+  std::sort(all.begin(), all.end());
+  for (size_t i = 0; i + 1 < all.size(); ++i) {
+    for (size_t j = i + 1; j < all.size() && all[j].first < all[i].first + words; ++j)
+      if (all[i].second || all[j].second)
+        throw std::invalid_argument("rotation batch: an output overlaps an input or another output");
+  }
+  const size_t chunk = rotate_fused_batch_chunk(ctx, chain_index);
+  for (size_t at = 0; at < count; at += chunk) {
+    const size_t c = std::min(chunk, count - at);
+    DeviceBuffer<uint64_t> slab(c * words, s);
+    rotate_chunk(ctx, chain_index, rt, cts + at, c, evk, galois_elt, slab.get(), s);
+    std::vector<phx::CopyPair> pairs(c);
+    for (size_t k = 0; k < c; ++k) pairs[k] = {slab.get() + k * words, outs[at + k]};
+    copy_table(pairs, words, s);
+  }
+}
+
+static std::vector<PhantomCiphertext> rotate_batch_elt(const PhantomContext& ctx,
+                                                       std::span<const PhantomCiphertext* const> cts,
+                                                       const PhantomGaloisKey& keys, uint32_t elt) {
+  std::vector<PhantomCiphertext> out(cts.size());
+  if (cts.empty()) return out;
+  for (const PhantomCiphertext* c : cts)
+    if (!c) throw std::invalid_argument("rotation batch: null ciphertext");
+  const size_t chain = cts[0]->chain_index();
+  for (const PhantomCiphertext* c : cts) {
+    if (c->size() != 2 || !c->is_ntt_form()) throw std::invalid_argument("rotation batch: 2-polynomial NTT-form inputs");
+    if (c->chain_index() != chain) throw std::invalid_argument("rotation batch: the inputs must share a chain index");
+  }
+  if (!keys.has(elt)) throw std::invalid_argument("rotation batch: no key for the rotation");
+  batch_tool(ctx, chain);
+  hipStream_t s = ctx.stream();
+  std::vector<const uint64_t*> in(cts.size());
+  std::vector<uint64_t*> o(cts.size());
+  for (size_t k = 0; k < cts.size(); ++k) {
+    out[k].resize(ctx, chain, 2, s, false);
+    out[k].set_scale(cts[k]->scale());
+    out[k].SetNoiseScaleDeg(cts[k]->GetNoiseScaleDeg());
+    out[k].set_ntt_form(true);
+    in[k] = cts[k]->data();
+    o[k] = out[k].data();
+  }
+  rotate_fused_batch_raw(ctx, chain, in.data(), in.size(), keys.get(elt).public_keys_ptr(), elt, o.data(), s);
+  return out;
+}
+
+std::vector<PhantomCiphertext> EvalRotateFusedBatch(const PhantomContext& ctx,
+                                                    std::span<const PhantomCiphertext* const> cts,
+                                                    const PhantomGaloisKey& keys, int index) {
+  return rotate_batch_elt(ctx, cts, keys, FindAutomorphismIndex2nComplex(index, ctx.poly_degree()));
+}
+
+std::vector<PhantomCiphertext> EvalConjFusedBatch(const PhantomContext& ctx,
+                                                  std::span<const PhantomCiphertext* const> cts,
+                                                  const PhantomGaloisKey& keys) {
+  return rotate_batch_elt(ctx, cts, keys, static_cast<uint32_t>(2 * ctx.poly_degree() - 1));
 }
 
 }  // namespace phantom

@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <span>
 #include <vector>
 
 #include "ciphertext.h"
@@ -191,6 +192,49 @@ inline void EvalConjFused(const PhantomContext& ctx, const PhantomGaloisKey& fus
                           PhantomCiphertext& out) {
   out = EvalConjFused(ctx, in, fused_keys);
 }
+
+// ---- batched same-key rotations: every ciphertext of `cts` rotated by `index` (conjugated) under
+// one Galois key.  Per chunk of at most rotate_fused_batch_chunk ciphertexts: one batched modup,
+// one phx::keyswitch_rotate_many (the key read once) and one moddown over 2 count polynomials, a
+// fixed number of launches whatever the count.  Output k equals EvalRotateFused (EvalConjFused) of
+// input k bit for bit, with or without the unbiased moddown, and takes input k's scale, noise-scale
+// degree and chain index; results do not depend on the chunking.  All on the context's stream, no
+// synchronisation, scratch from the pool freed in stream order.
+// std::invalid_argument before anything is enqueued: inputs at different chain indices, an input
+// that is not a 2-polynomial NTT-form ciphertext, a null entry, a missing key.  An empty span gives
+// an empty vector.
+std::vector<PhantomCiphertext> EvalRotateFusedBatch(const PhantomContext& ctx,
+                                                    std::span<const PhantomCiphertext* const> cts,
+                                                    const PhantomGaloisKey& fused_keys, int index);
+std::vector<PhantomCiphertext> EvalConjFusedBatch(const PhantomContext& ctx,
+                                                  std::span<const PhantomCiphertext* const> cts,
+                                                  const PhantomGaloisKey& fused_keys);
+// Scratch cap of one chunk.  A ciphertext of a chunk takes (6 Ql + (beta + 2) QlP) n words: the
+// staged c1 and the modup's INTT (Ql each), the digits (beta QlP), the extended result (2 QlP), the
+// moddown's delta and the output slab (2 Ql each); the modup's and moddown's two stay with the
+// context's workspace.  The chunk is min(64, cap / that), at least 1.  A batch draws its whole chunk's
+// scratch from the pool at once (80 MiB per ciphertext at N = 2^16 and 12 limbs: 2.5 GiB for 32), where
+// one-at-a-time rotations draw one ciphertext's; a lower cap shrinks the chunk and changes no result.
+constexpr size_t kRotateBatchScratchBytes = size_t(4) << 30;
+size_t rotate_fused_batch_chunk(const PhantomContext& ctx, size_t chain_index);
+// Raw forms on host arrays of device pointers (the C-ABI's), enqueued on `s`.  cts[k] [2][Ql][n] at
+// `chain_index`; evk: device array of the key's digit pointers (PhantomKSwitchKey::public_keys_ptr).
+// std::invalid_argument before anything is enqueued: a null pointer, a bad chain index, a buffer
+// not 16-byte aligned, an output overlapping an input or another output.
+// The kernel alone: outs[k] [2][QlP][n] = EvalFastAutomorphismExt(cts[k], digits[k], add_first),
+// digits[k] [beta][QlP][n]; count 1..64
+void keyswitch_rotate_many_raw(const PhantomContext& ctx, size_t chain_index, size_t count, const uint64_t* const* cts,
+                               const uint64_t* const* digits, const uint64_t* const* evk, uint32_t galois_elt,
+                               uint64_t* const* outs, hipStream_t s);
+// the whole rotation of one chunk (count <= rotate_fused_batch_chunk) into slab [count][2][Ql][n]:
+// the inputs' c1 are staged side by side for the batched modup (one copy launch; Ql n words read
+// and written per ciphertext), the results stay in the slab
+void rotate_fused_batch_slab(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, size_t count,
+                             const uint64_t* const* evk, uint32_t galois_elt, uint64_t* slab, hipStream_t s);
+// any count, chunked, into separate buffers outs[k] [2][Ql][n]: the slab form plus one copy launch
+// per chunk (2 Ql n words read and written per ciphertext)
+void rotate_fused_batch_raw(const PhantomContext& ctx, size_t chain_index, const uint64_t* const* cts, size_t count,
+                            const uint64_t* const* evk, uint32_t galois_elt, uint64_t* const* outs, hipStream_t s);
 
 // Galois element of a slot rotation (FindAutomorphismIndex2nComplex, src/util.cu:908-935)
 uint32_t FindAutomorphismIndex2nComplex(int index, size_t n);

@@ -492,9 +492,21 @@ TensorCT DNN::Unpack(const PackedCT& packed) {
   out.width_ = packed.width_;
   out.slotstr_ = packed.slotstr_;
   out.num_ch_ = packed.num_ch_;
-  for (size_t grp = 0; grp < packed.ctks_.size(); ++grp)
-    for (PhantomCiphertext& c : unpack_channels(context_, plan, packed.ctks_[grp], plan.members(packed.num_ch_, grp), gk_))
-      out.ctks_.push_back(std::move(c));
+  if (unpack_path_ == UnpackPath::kPerNode) {
+    for (size_t grp = 0; grp < packed.ctks_.size(); ++grp)
+      for (PhantomCiphertext& c : unpack_channels(context_, plan, packed.ctks_[grp], plan.members(packed.num_ch_, grp), gk_))
+        out.ctks_.push_back(std::move(c));
+    return out;
+  }
+  // every group's tree level by level, one batched rotation per level (host/pack.h): the same words
+  std::vector<const PhantomCiphertext*> groups(packed.ctks_.size());
+  std::vector<size_t> members(packed.ctks_.size());
+  for (size_t grp = 0; grp < packed.ctks_.size(); ++grp) {
+    groups[grp] = &packed.ctks_[grp];
+    members[grp] = plan.members(packed.num_ch_, grp);
+  }
+  for (std::vector<PhantomCiphertext>& g : unpack_channels_batch(context_, plan, groups, members, gk_))
+    for (PhantomCiphertext& c : g) out.ctks_.push_back(std::move(c));
   return out;
 }
 

@@ -193,6 +193,14 @@ class DNN {
   // the rotation tree (pack - 1 key switches for a full group): level, degree and scale() of the packed
   // input; every channel's message is pack_ times the packed one's
   TensorCT Unpack(const PackedCT& packed);
+  // how Unpack (and BootStrap / ReluComposite through it) walks the tree: kBatched takes every group's
+  // tree level by level through unpack_channels_batch (one batched key switch per level), kPerNode
+  // one EvalRotateFused per node through unpack_channels.  The outputs are the same words either way;
+  // kBatched is the default: faster at each ResNet-20 stage ("Batched same-key rotations",
+  // has the times of both), at a level's worth of scratch drawn from the pool at once.
+  enum class UnpackPath { kBatched, kPerNode };
+  void set_unpack_path(UnpackPath p) { unpack_path_ = p; }
+  UnpackPath unpack_path() const { return unpack_path_; }
   // pack = 1: every channel through EvalBootstrapBatch at ns slots (src/dnn.cu:263-275).  pack = P > 1:
   // rescale a degree-2 input, Pack, EvalBootstrapBatch of the groups at P ns slots with
   // post_shift = log2 P (the tree's factor P is taken out of the bootstrap's closing integer: no
@@ -229,6 +237,7 @@ class DNN {
 
   size_t scale_;
   PhantomGaloisKeyFused gk_;
+  UnpackPath unpack_path_ = UnpackPath::kBatched;
   const PhantomContext& context_;
   PhantomCKKSEncoder& encoder_;
   std::vector<double> m_scalingFactorsReal_;

@@ -229,4 +229,75 @@ std::vector<PhantomCiphertext> unpack_channels(const PhantomContext& ctx, const 
   return out;
 }
 
+std::vector<std::vector<PhantomCiphertext>> unpack_channels_batch(const PhantomContext& ctx, const PackPlan& plan,
+                                                                  std::span<const PhantomCiphertext* const> packed,
+                                                                  std::span<const size_t> channels,
+                                                                  const PhantomGaloisKey& keys) {
+  const size_t G = packed.size();
+  if (channels.size() != G) throw std::invalid_argument("unpack_channels_batch: one channel count per group");
+  if (plan.n != ctx.poly_degree()) throw std::invalid_argument("unpack_channels_batch: the plan is for another ring degree");
+  for (size_t g = 0; g < G; ++g) {
+    if (!packed[g]) throw std::invalid_argument("unpack_channels_batch: null group");
+    if (channels[g] < 1 || channels[g] > plan.pack) throw std::invalid_argument("unpack_channels_batch: 1 to pack channels");
+    if (packed[g]->size() != 2 || !packed[g]->is_ntt_form())
+      throw std::invalid_argument("unpack_channels_batch: a 2-polynomial NTT-form input");
+    if (packed[g]->chain_index() != packed[0]->chain_index())
+      throw std::invalid_argument("unpack_channels_batch: the groups must share a chain index");
+  }
+  for (uint32_t e : plan.galois)
+    if (!keys.has(e)) throw std::invalid_argument("unpack_channels_batch: no rotation key for a tree level (AddPackRotationsTo)");
+  std::vector<std::vector<PhantomCiphertext>> out(G);
+  if (G == 0) return out;
+  const size_t chain = packed[0]->chain_index(), words = 2 * checked_limbs(ctx, chain) * ctx.poly_degree();
+  const size_t chunk = std::min(rotate_fused_batch_chunk(ctx, chain), static_cast<size_t>(phx::kSplitMax));
+  hipStream_t s = ctx.stream();
+  std::vector<std::vector<PhantomCiphertext>> node(G);
+  std::vector<std::vector<bool>> have(G, std::vector<bool>(plan.pack, false));
+  for (size_t g = 0; g < G; ++g) {
+    node[g].resize(plan.pack);
+    node[g][0] = *packed[g];
+    have[g][0] = true;
+  }
+  for (size_t t = 0; t < plan.log_pack; ++t) {
+    const size_t half = size_t(1) << t;
+    // the level's live nodes of every group, in unpack_channels' order within a group: they share the key
+    std::vector<const uint64_t*> a;
+    std::vector<uint64_t*> even, odd;
+    std::vector<PhantomCiphertext*> spent;  // nodes whose even child is pruned: read by this level only
+    for (size_t g = 0; g < G; ++g)
+      for (size_t idx = 0; idx < half; ++idx) {
+        if (!have[g][idx]) continue;
+        const size_t child = idx | half;
+        const bool ev = plan.needed(idx, t + 1, channels[g]), od = plan.needed(child, t + 1, channels[g]);
+        if (od) like(ctx, *packed[g], node[g][child]);
+        if (!ev) spent.push_back(&node[g][idx]);
+        a.push_back(node[g][idx].data());
+        even.push_back(ev ? node[g][idx].data() : nullptr);
+        odd.push_back(od ? node[g][child].data() : nullptr);
+        have[g][idx] = ev;
+        have[g][child] = od;
+      }
+    const uint64_t* const* evk = keys.get(plan.galois[t]).public_keys_ptr();
+    for (size_t at = 0; at < a.size(); at += chunk) {
+      const size_t c = std::min(chunk, a.size() - at);
+      // the rotated nodes stay in the batch's slab: ct_split takes a pointer per node
+      DeviceBuffer<uint64_t> slab(c * words, s);
+      rotate_fused_batch_slab(ctx, chain, a.data() + at, c, evk, plan.galois[t], slab.get(), s);
+      std::vector<const uint64_t*> r(c);
+      for (size_t k = 0; k < c; ++k) r[k] = slab.get() + k * words;
+      ct_split_raw(ctx, chain, a.data() + at, r.data(), c, plan.powers[t], even.data() + at, odd.data() + at, s);
+    }
+    // back to the pool in stream order, after the level's splits that read them
+    for (PhantomCiphertext* c : spent) {
+      c->retag(s);
+      *c = PhantomCiphertext();
+    }
+  }
+  for (size_t g = 0; g < G; ++g) {
+    out[g].resize(channels[g]);
+    for (size_t c = 0; c < channels[g]; ++c) out[g][c] = std::move(node[g][plan.lead(channels[g]) + c]);
+  }
+  return out;
+}
+
 }  // namespace phantom

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <span>
 #include <vector>
 
 #include "ciphertext.h"
@@ -83,5 +84,16 @@ PhantomCiphertext pack_channels(const PhantomContext& ctx, const PackPlan& plan,
 // std::invalid_argument when `keys` lacks a rotation of the plan that the C channels need
 std::vector<PhantomCiphertext> unpack_channels(const PhantomContext& ctx, const PackPlan& plan,
                                                const PhantomCiphertext& packed, size_t C, const PhantomGaloisKey& keys);
+// the trees of several groups level by level: the live nodes of ALL groups at a level share the
+// level's key, so they go through one batched rotation (rotate_fused_batch_slab, host/ckks_eval.h:
+// one modup, one key switch with the key read once, one moddown) per chunk of min(its chunk size,
+// phx::kSplitMax) nodes and one ct_split on the rotated nodes where they lie in the batch's slab.
+// Pruning, the lead rule and the output order are unpack_channels'; result [g] equals
+// unpack_channels(ctx, plan, *packed[g], channels[g], keys) word for word.  The groups share a chain
+// index (std::invalid_argument otherwise, and as unpack_channels), before anything is enqueued.
+std::vector<std::vector<PhantomCiphertext>> unpack_channels_batch(const PhantomContext& ctx, const PackPlan& plan,
+                                                                  std::span<const PhantomCiphertext* const> packed,
+                                                                  std::span<const size_t> channels,
+                                                                  const PhantomGaloisKey& keys);
 
 }  // namespace phantom

@@ -147,6 +147,11 @@ _SIGS = {
     "phantom_ct_pack": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), sz, ctypes.c_uint32, vp, vp]),
     "phantom_ct_split": (ctypes.c_int, [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(vp), sz, ctypes.c_uint32,
                                         ctypes.POINTER(vp), ctypes.POINTER(vp), vp]),
+    "phantom_keyswitch_rotate_many": (ctypes.c_int, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                                     ctypes.POINTER(vp), sz, ctypes.c_uint32, ctypes.POINTER(vp), vp]),
+    "phantom_rotate_fused_batch": (ctypes.c_int, [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(vp), sz,
+                                                  ctypes.c_uint32, ctypes.POINTER(vp), vp]),
+    "phantom_rotate_fused_batch_chunk": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
     "phantom_conv_rotations": (ctypes.c_int, [sz, sz, sz, vp, sz, ctypes.POINTER(sz)]),
     "phantom_conv_weight_slots": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp, vp]),
     "phantom_conv_weight_slots_host": (ctypes.c_int, [sz, sz, sz, sz, sz, vp, sz, sz, vp]),
@@ -609,6 +614,32 @@ class ConvPlan:
 
 def ptr_array(ptrs):
     return (vp * len(ptrs))(*ptrs)
+
+
+def rotate_fused_batch_chunk(ctx, chain_index):
+    """ciphertexts of one chunk of rotate_fused_batch at chain_index (host only)"""
+    c = sz(0)
+    check(load().phantom_rotate_fused_batch_chunk(ctx.handle, chain_index, ctypes.byref(c)))
+    return c.value
+
+
+def rotate_fused_batch(ctx, chain_index, cts, key_digits, dnum, galois_elt, outs, stream):
+    """every ciphertext of cts ([2][Ql][n] device pointers) rotated under one key into outs: sequences of
+    device pointers (or ctypes arrays of them); key_digits: ctypes array of dnum device pointers"""
+    assert len(cts) == len(outs)
+    a = cts if isinstance(cts, ctypes.Array) else ptr_array(list(cts))
+    o = outs if isinstance(outs, ctypes.Array) else ptr_array(list(outs))
+    check(load().phantom_rotate_fused_batch(ctx.handle, chain_index, len(cts), a, key_digits, dnum, galois_elt, o,
+                                            stream))
+
+
+def keyswitch_rotate_many(ctx, chain_index, cts, digits, key_digits, dnum, galois_elt, outs, stream):
+    """the batched key switch alone: outs[k] [2][Ql+P][n] from cts[k]'s c0 and digits[k] [beta][Ql+P][n],
+    1 to 64 ciphertexts in one launch"""
+    assert len(cts) == len(digits) == len(outs)
+    check(load().phantom_keyswitch_rotate_many(ctx.handle, chain_index, len(cts), ptr_array(list(cts)),
+                                               ptr_array(list(digits)), key_digits, dnum, galois_elt,
+                                               ptr_array(list(outs)), stream))
 
 
 class NttTables:
