@@ -6,7 +6,14 @@
  * is poly-major data[(poly * L + limb) * n + k], every value in [0, q_limb).  All compute
  * entry points enqueue asynchronously on the given stream (the reference hard-codes
  * cudaStreamPerThread, e.g. src/evaluate.cu:1200) and return a status code instead of
- * throwing.
+ * throwing.  The entries that copy a pointer or entry table from host memory, or build tables
+ * for one call, wait for `stream` once before they return (everything else returns while the
+ * stream still runs; tests/test_gpu_stream_order.py holds both lists to the code):
+ *   phantom_fast_bconv, phantom_bconv_create, phantom_lt_bsgs, phantom_lt_bsgs_group,
+ *   phantom_fast_rotation_ext_batch_group, phantom_leaf_combine, phantom_ext_mac,
+ *   phantom_ext_mac_sub, phantom_ext_mac_sub_seeded, phantom_rotate_sum_ext,
+ *   phantom_conv2d_prepare, phantom_conv2d_prepare_scaled, phantom_ltprep_stage_products,
+ *   phantom_ltprep_presence, phantom_ltprep_finish.
  *
  * Each entry point names the reference interface it replaces (file:line, relative to the
  * PhantomFHE repository root).

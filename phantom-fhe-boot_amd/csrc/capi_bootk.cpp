@@ -5,6 +5,7 @@
 // MulAddRescale's linear epilogue (tensor_lin), the Chebyshev leaves (leaf_combine) and the
 // per-limb scalar kernels.  Host arrays of device pointers and of per-limb residues are copied into
 // the kernels' argument blocks or small device tables here (set-up cost, not on the hot path).
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -14,6 +15,7 @@
 #include "../host/context.h"
 #include "../host/numth.h"
 #include "ckks.h"
+#include "conv.h"
 #include "phantom_amd.h"
 #include "rns.h"
 
@@ -138,11 +140,20 @@ int phantom_fast_rotation_ext_batch(const phantom_context* ctx, size_t chain_ind
       }
       e[k].out_off = outs[k] - outs[0];
     }
-    phantom::DeviceBuffer<phx::KsBatchEntry> table;
-    table.upload(e, stream);
+    // the entry table in stream order, without a host-to-device copy and its wait (phx::write_words)
+    static_assert(sizeof(phx::KsBatchEntry) % sizeof(uint64_t) == 0, "entries are copied as words");
+    const size_t entry_words = count * sizeof(phx::KsBatchEntry) / sizeof(uint64_t);
+    phantom::DeviceBuffer<uint64_t> table(entry_words, stream);
+    for (size_t w0 = 0; w0 < entry_words; w0 += phx::kWordsMax) {
+      const size_t cnt = std::min<size_t>(phx::kWordsMax, entry_words - w0);
+      phx::Words w;
+      std::memcpy(w.w, reinterpret_cast<const uint64_t*>(e.data()) + w0, cnt * sizeof(uint64_t));
+      const hipError_t we = phx::write_words(table.get() + w0, w, cnt, stream);
+      if (we != hipSuccess) return from_hip(we);
+    }
     phx::KsRotateBatchArgs a;
     a.digits = digits;
-    a.entries = table.get();
+    a.entries = reinterpret_cast<const phx::KsBatchEntry*>(table.get());
     a.count = static_cast<uint32_t>(count);
     a.qp = pc.mod_QP().q;
     a.qp_barrett = pc.mod_QP().barrett;
