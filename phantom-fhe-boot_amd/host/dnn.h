@@ -17,7 +17,7 @@
 // PrepareConvBN / ConvAdd fold the batch norm and the residual add of a residual block into the
 // prepared convolution (one level instead of two; host/conv2d.h "fused affine terms").
 //
-// Not built here: SoftMax, the weight loader and the ResNet driver.
+// The weight loader is host/npy.h and the ResNet driver host/resnet.h.  Not built: SoftMax.
 #pragma once
 
 #include <cstdint>
